@@ -28,6 +28,13 @@ WORLD_SIZE == N.
 with position control on ODE's QuickStep, hs_sim_step): a step is one
 simulation step (play_dt) of every rollout; K steps run in one launch.
 
+A plain run sets up, warms up, times the K steps and prints the result line. --full adds what the
+headline figure does not need: the CPU baseline (the oracle's restatement, --cpu-seconds of it, unless
+--no-cpu) and the untimed checks of the run's outputs (the best key against its host-side encoding and
+the NaN-step count; the state's finiteness for --sim; the forces against the control loop's for
+--forces). --dump-outputs DIR writes what the timed job computed in its last step as DIR/<name>.npy
+(dump_outputs).
+
 --stub-cpu (tests/test_bench_launcher.py): the same launcher, sharding, key encoding and
 max-over-ranks timing on CPU ranks over gloo, with a stub in place of the GPU kernel.
 """
@@ -83,9 +90,16 @@ def parse(argv=None):
                     help="solve_forces (contact forces given motor torques, ftsolver.cpp:331-378) steps/s: "
                          "the K steps' torques from an untimed control-loop run, then K fused steps "
                          "(hs_run_forces_calls)")
+    ap.add_argument("--full", action="store_true",
+                    help="also what the headline figure does not need: the CPU baseline (see --no-cpu) and the "
+                         "untimed checks of the run's outputs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays the timed job computed in its last step as "
+                         "DIR/<name>.npy (float32 / float64, at most 64 MB: a fixed seeded sample of the rollouts "
+                         "beyond that); the inputs are the same from run to run")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--cpu-threads", type=int, default=None, help="default: the host cores this process may use")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--stub-cpu", action="store_true", help=argparse.SUPPRESS)
     return ap.parse_args(argv)
 
@@ -309,7 +323,9 @@ def main_sim(args, torch, dist, world, rank, dev):
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed, kern_ms = float(t[0]), float(t[1])
-    finite = bool(torch.isfinite(sb.body).all().item())
+    finite = bool(torch.isfinite(sb.body).all().item()) if args.full else None
+    if args.dump_outputs:  # the state the launch of K steps leaves (it was asked for no per-step outputs)
+        dump_outputs(args.dump_outputs, {"body": sb.body, "tsi": sb.tsi}, rank, world)
     if rank == 0:
         nmj = model.nmj
         # per rollout-step the kernel must read the controller row (q0, dq0, tau_ff: 3 nmj reals);
@@ -330,10 +346,11 @@ def main_sim(args, torch, dist, world, rank, dev):
             "roofline": {"bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": None, "kernel": "hs_sim_kernel",
                          "kernel_ms": round(kern_ms, 5), "alg_bytes_per_launch": alg_bytes},
-            "finite_state": finite,
         }
-        out["cpu_baseline"] = None if (args.no_cpu or world > 1) else sim_cpu_baseline(
-            model, args.model, sb, args.cpu_seconds, args.cpu_threads)
+        if args.full:
+            out["finite_state"] = finite
+            out["cpu_baseline"] = None if (args.no_cpu or world > 1) else sim_cpu_baseline(
+                model, args.model, sb, args.cpu_seconds, args.cpu_threads)
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
@@ -426,9 +443,12 @@ def main_forces(args, torch, dist, world, rank, dev):
     elapsed, kern_ms = float(t[0]), float(t[1])
     # untimed check (playerexperim.cpp:95-121): the forces that realise the computed torques are the
     # computed contact forces
-    cf, ref = fb.cf[:, :K].double(), ctl.cf[:, :K].double()
-    err = float(((cf - ref).abs().amax(dim=2) / ref.abs().amax(dim=2).clamp(min=1)).max().item())
-    general = int(((fb.flags[:, :K] & capi.HS_FLAG_GENERAL) != 0).sum().item())
+    if args.full:
+        cf, ref = fb.cf[:, :K].double(), ctl.cf[:, :K].double()
+        err = float(((cf - ref).abs().amax(dim=2) / ref.abs().amax(dim=2).clamp(min=1)).max().item())
+        general = int(((fb.flags[:, :K] & capi.HS_FLAG_GENERAL) != 0).sum().item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"cf": fb.cf[:, K - 1], "flags": fb.flags[:, K - 1]}, rank, world)
     if rank == 0:
         nmj, nf = model.nmj, model.nfeet
         step_bytes = 8 * (nmj + 3 * nf) + PARAM_BYTES  # torques in, forces of all feet out, the gait record
@@ -451,12 +471,13 @@ def main_forces(args, torch, dist, world, rank, dev):
                          "traffic_note": pmc_note, "kernel": step_kernel([model], forces=True),
                          "kernel_ms": round(kern_ms, 5), "alg_bytes_per_launch": alg_bytes,
                          "alg_bytes_per_step": step_bytes},
-            "check": {"max_rel_cf_vs_control_loop": err, "general_steps": general},
             "lib": lib,
         }
-        nb = min(B, 256)
-        out["cpu_baseline"] = None if (args.no_cpu or world > 1) else forces_cpu_baseline(
-            args.model, params[:nb], ctl.tau[:nb, :K].cpu().numpy(), n_t, args.cpu_seconds, args.cpu_threads)
+        if args.full:
+            out["check"] = {"max_rel_cf_vs_control_loop": err, "general_steps": general}
+            nb = min(B, 256)
+            out["cpu_baseline"] = None if (args.no_cpu or world > 1) else forces_cpu_baseline(
+                args.model, params[:nb], ctl.tau[:nb, :K].cpu().numpy(), n_t, args.cpu_seconds, args.cpu_threads)
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
@@ -496,6 +517,48 @@ def flops_for(workload_key):
     if not j:
         return None
     return (j.get("workloads") or {}).get(workload_key)
+
+
+# ---------------------------------------------------------------------------------------------
+# --dump-outputs
+# ---------------------------------------------------------------------------------------------
+DUMP_BUDGET = 60_000_000  # bytes over all arrays of one rank: under 64 MB with the files' headers
+DUMP_SEED = 0
+
+
+def last_step_rows(t, B, n_rows, Hh):
+    """The rows of the job's last step in an output buffer of the fused launches: the buffer holds
+    [B][n_rows][...] packed from its start (hs_run_calls; n_rows = K * Hh can be less than the rows
+    allocated when the warmup is longer than the timed job)."""
+    d = t[0, 0].numel()
+    return t.reshape(-1)[:B * n_rows * d].view(B, n_rows, *t.shape[2:])[:, n_rows - Hh:]
+
+
+def dump_outputs(dirname, arrays, rank=0, world=1):
+    """DIR/<name>.npy (rank r of several: <name>.rank<r>.npy) for every tensor of `arrays`, float32
+    and float64 as they are, integers as float64. Arrays of one row per rollout share the budget:
+    beyond DUMP_BUDGET bytes the same seeded sample of the rollouts (sorted; rollout_rows.npy) is
+    kept of each of them."""
+    import torch
+
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: v for k, v in arrays.items() if v is not None}
+    width = {k: (v.element_size() if v.dtype in (torch.float32, torch.float64) else 8) for k, v in arrays.items()}
+    total = sum(v.numel() * width[k] for k, v in arrays.items())
+    B = max(len(v) for v in arrays.values())
+    rows = None
+    if total > DUMP_BUDGET:
+        keep = max(1, int(B * (DUMP_BUDGET - 8 * B) / total))
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(B, size=keep, replace=False))
+        arrays["rollout_rows"] = torch.from_numpy(rows)
+    suffix = f".rank{rank}" if world > 1 else ""
+    for name, t in arrays.items():
+        if rows is not None and name != "rollout_rows" and len(t) == B:
+            t = t[torch.from_numpy(rows).to(t.device)]
+        a = t.detach().cpu().numpy()
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), np.ascontiguousarray(a))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -721,17 +784,28 @@ def main():
     elapsed, kern_ms = float(t[0]), float(t[1])
     key = batch.best_key.clone()
 
-    # untimed checks: the device key equals the host-side encoding of the accumulated work, reduced
-    # over the ranks by torch.distributed; NaN outputs are counted
-    p_dev = torch.from_numpy(np.ascontiguousarray(params["step_length"])).to(dev)
-    sel = hdist.select_cot(batch.work_cot[:, 0], p_dev, mass, n_t, args.steps * Hh)
-    check = hdist.reduce_best(hdist.best_key(sel, id0))
-    if int(check.item()) != int(key.item()) ^ hdist._FLIP:
-        raise RuntimeError(f"best key mismatch: device {int(key.item())} vs host {int(check.item()) ^ hdist._FLIP}")
-    best_cot, best_id = hdist.decode(check)
-    nan_steps = torch.tensor([int(((batch.flags & 8) != 0).sum().item())], device=dev)
-    if world > 1:
-        dist.all_reduce(nan_steps)
+    # --full, untimed checks: the device key equals the host-side encoding of the accumulated work,
+    # reduced over the ranks by torch.distributed; NaN outputs are counted
+    if args.full:
+        p_dev = torch.from_numpy(np.ascontiguousarray(params["step_length"])).to(dev)
+        sel = hdist.select_cot(batch.work_cot[:, 0], p_dev, mass, n_t, args.steps * Hh)
+        check = hdist.reduce_best(hdist.best_key(sel, id0))
+        if int(check.item()) != int(key.item()) ^ hdist._FLIP:
+            raise RuntimeError(f"best key mismatch: device {int(key.item())} vs host {int(check.item()) ^ hdist._FLIP}")
+        best_cot, best_id = hdist.decode(check)
+        nan_steps = torch.tensor([int(((batch.flags & 8) != 0).sum().item())], device=dev)
+        if world > 1:
+            dist.all_reduce(nan_steps)
+    if args.dump_outputs:
+        # what a caller of the job receives of its last step: that step's rows of the per-step outputs,
+        # the work and COT accumulated up to it, and the best key the job left (COT, rollout id)
+        n_rows = args.steps * Hh
+        last = (lambda t: last_step_rows(t, B, n_rows, Hh)) if fused else (lambda t: t)
+        key_cot, key_id = hdist.decode(key ^ hdist._FLIP)
+        dump_outputs(args.dump_outputs,
+                     {"tau": last(batch.tau), "cf": last(batch.cf), "flags": last(batch.flags),
+                      "work_cot": batch.work_cot,
+                      "best_key": torch.tensor([key_cot, float(key_id)], dtype=torch.float64)}, rank, world)
     if comm is not None:
         comm.free()
 
@@ -778,14 +852,15 @@ def main():
                          "kernel_ms": round(kern_ms, 5), "alg_bytes_per_launch": alg_bytes},
             # the bound that binds: FP64 VALU issue/latency
             "fp64_valu": fp64,
-            "best_rollout": {"id": best_id, "cot_per_cycle": best_cot},
-            "nan_steps": int(nan_steps.item()),
             "lib": lib,
         }
-        if not args.no_cpu and world == 1:
-            out["cpu_baseline"] = cpu_baseline(model_names, n_t, Hh, args.cpu_seconds, args.cpu_threads)
-        else:
-            out["cpu_baseline"] = None
+        if args.full:
+            out["best_rollout"] = {"id": best_id, "cot_per_cycle": best_cot}
+            out["nan_steps"] = int(nan_steps.item())
+            if not args.no_cpu and world == 1:
+                out["cpu_baseline"] = cpu_baseline(model_names, n_t, Hh, args.cpu_seconds, args.cpu_threads)
+            else:
+                out["cpu_baseline"] = None
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()

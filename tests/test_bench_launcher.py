@@ -109,3 +109,53 @@ def test_every_bench_mode_times_through_timed_window():
     calls = []
     el = bench.timed_window(lambda: calls.append("job"), lambda: calls.append("sync"))
     assert calls == ["job", "sync"] and el >= 0
+
+
+def test_full_and_dump_outputs_are_off_by_default():
+    import bench
+
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    a = bench.parse(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+
+
+def test_last_step_rows_of_a_packed_output_buffer():
+    """hs_run_calls packs [B][K * H][d] from the buffer's start, whatever rows the buffer was allocated with"""
+    import bench
+
+    B, K, H, d, alloc = 5, 3, 2, 4, 8
+    buf = torch.full((B, alloc, d), -1.0, dtype=torch.float64)
+    packed = torch.arange(B * K * H * d, dtype=torch.float64).view(B, K * H, d)
+    buf.view(-1)[:packed.numel()] = packed.view(-1)
+    assert torch.equal(bench.last_step_rows(buf, B, K * H, H), packed[:, (K - 1) * H:])
+    flags = torch.arange(B * alloc, dtype=torch.int32).view(B, alloc)
+    assert torch.equal(bench.last_step_rows(flags, B, K * H, H), flags.view(-1)[:B * K * H].view(B, K * H)[:, -H:])
+
+
+def test_dump_outputs_formats_and_seeded_sample(tmp_path, monkeypatch):
+    import bench
+
+    g = torch.Generator().manual_seed(1)
+    arrays = {"tau": torch.randn(100, 2, 3, generator=g), "cf": torch.randn(100, 2, 6, generator=g).double(),
+              "flags": torch.arange(200, dtype=torch.int32).view(100, 2), "best_key": torch.tensor([0.5, 7.0]),
+              "none": None}
+    bench.dump_outputs(str(tmp_path / "all"), arrays)
+    got = {f: np.load(tmp_path / "all" / f) for f in os.listdir(tmp_path / "all")}
+    assert set(got) == {"tau.npy", "cf.npy", "flags.npy", "best_key.npy"}
+    assert got["tau.npy"].dtype == np.float32 and got["cf.npy"].dtype == np.float64
+    assert got["flags.npy"].dtype == np.float64 and np.array_equal(got["flags.npy"], arrays["flags"].numpy())
+    assert np.array_equal(got["tau.npy"], arrays["tau"].numpy())
+    # over the budget: the same seeded rollouts of every per-rollout array, the same in a second run
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 4000)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), arrays, rank=1, world=2)
+    s1 = {f: np.load(tmp_path / "s1" / f) for f in os.listdir(tmp_path / "s1")}
+    s2 = {f: np.load(tmp_path / "s2" / f) for f in os.listdir(tmp_path / "s2")}
+    assert set(s1) == {n + ".rank1.npy" for n in ("tau", "cf", "flags", "best_key", "rollout_rows")}
+    assert sum(a.nbytes for a in s1.values()) <= 4000
+    rows = s1["rollout_rows.rank1.npy"].astype(int)
+    assert 1 <= len(rows) < 100 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(s1["cf.rank1.npy"], arrays["cf"].numpy()[rows])
+    assert np.array_equal(s1["best_key.rank1.npy"], arrays["best_key"].numpy())
+    assert all(np.array_equal(s1[f], s2[f]) for f in s1)

@@ -10,7 +10,7 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -v -s --timeout 300 --time
 tail -1 $OUT/tests.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { echo smoke failed; cat $OUT/smoke.log; exit 1; }
 tail -1 $OUT/smoke.log
-timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver.json 2> $OUT/bench_driver.err || { echo bench failed; tail -20 $OUT/bench_driver.err; exit 1; }
+timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_driver.json 2> $OUT/bench_driver.err || { echo bench failed; tail -20 $OUT/bench_driver.err; exit 1; }
 python -c "import json;d=json.load(open('$OUT/bench_driver.json'));print('driver', round(d['value']/1e6,2), 'M; kernel us/step', round(d['roofline']['kernel_ms']*1e3,3), 'cpu', d['cpu_baseline']['value'])"
 for i in 1 2 3; do
   timeout -k 10 120 python bench.py --no-cpu --steps 20 --warmup 5 > $OUT/rep.json 2>>$OUT/rep.err || { tail -5 $OUT/rep.err; exit 1; }
@@ -20,7 +20,7 @@ for i in 1 2; do
   timeout -k 10 120 python bench.py --no-cpu --steps 200 --warmup 20 > $OUT/k200.json 2>>$OUT/rep.err || { tail -5 $OUT/rep.err; exit 1; }
   python -c "import json;d=json.load(open('$OUT/k200.json'));print('K=200', round(d['value']/1e6,2), 'M; kernel us/step', round(d['roofline']['kernel_ms']*1e3,3))" | tee -a $OUT/repeats.txt
 done
-timeout -k 10 300 python bench.py --forces --steps 20 --warmup 5 > $OUT/bench_forces.json 2> $OUT/bench_forces.err || { echo forces failed; tail -20 $OUT/bench_forces.err; exit 1; }
+timeout -k 10 300 python bench.py --forces --steps 20 --warmup 5 --full > $OUT/bench_forces.json 2> $OUT/bench_forces.err || { echo forces failed; tail -20 $OUT/bench_forces.err; exit 1; }
 python -c "import json;d=json.load(open('$OUT/bench_forces.json'));print('forces', round(d['value']/1e6,2), 'M; kernel us/step', round(d['roofline']['kernel_ms']*1e3,3))"
 for w in "--model spider --rollouts 16384 --horizon 32 --fp32" "--model spider --rollouts 16384 --horizon 32" "--mixed" "--model myant" "--rollouts 32768" "--curved" "--sim" "--sim --fp32 --model spider --rollouts 16384"; do
   timeout -k 10 180 python -u bench.py --no-cpu $w >> $OUT/other_workloads.jsonl 2>>$OUT/other.err || { echo "other workload failed: $w"; tail -5 $OUT/other.err; exit 1; }
