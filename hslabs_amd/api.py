@@ -657,6 +657,89 @@ class SimBatch:
         capi.check(capi.load().hs_sim_step(self.model.handle, ctypes.byref(a)), "hs_sim_step")
         return out
 
+    def trial(self, n_steps: int, *, open_loop: bool = False, torque_limit: float = 0.0, kick_every: int = 0,
+              kick_phase: int | None = None, kick_dv=None, hc: float = 0.0, check_from: int = 0,
+              check_until: int = -1, stream=None, **outputs) -> dict:
+        """n_steps of the fall test's simulate_ode (hs_sim_trial, one launch): open-loop torques, the
+        torque limit, torso kicks (kick_dv [B][3], a velocity change every kick_every steps at tsi %
+        kick_every == kick_phase; kick_phase None = kick_every - 1, the reference's) and the fall
+        check (root height < hc for check_from <= tsi <= check_until; check_until < 0: no end).
+        A fallen or survived rollout is frozen and keeps its state over later calls;
+        ``self.state`` [B] holds HS_TRIAL_RUNNING, HS_TRIAL_SURVIVED or the tsi of the fall,
+        ``self.fall_z`` the height its check saw. Returns ``state`` and ``fall_z`` with the requested
+        per-step outputs, named as keywords (``torso=True``: a fresh tensor; ``torso=tensor``: that
+        tensor; none named: all five, as step()). Rows a frozen rollout did not reach keep what they
+        held (NaN in fresh floating-point tensors, -1 in n_contacts)."""
+        torch = self.torch
+        B, nmj = self.B, self.model.nmj
+        if not hasattr(self, "state"):
+            self.state = torch.full((B,), capi.HS_TRIAL_RUNNING, dtype=torch.int32, device=self.device)
+            self.fall_z = torch.full((B,), float("nan"), dtype=self.dtype, device=self.device)
+        shapes = {"tau_cmd": (B, n_steps, nmj), "q_meas": (B, n_steps, nmj), "torso": (B, n_steps, 3),
+                  "n_contacts": (B, n_steps), "normal_force": (B, n_steps)}
+        if not outputs:
+            outputs = dict.fromkeys(shapes, True)
+        res = {}
+        for k, v in outputs.items():
+            if k not in shapes:
+                raise TypeError(f"unknown output {k}")
+            if v is False or v is None:
+                continue
+            if v is not True:
+                res[k] = v
+            elif k == "n_contacts":
+                res[k] = torch.full(shapes[k], -1, dtype=torch.int32, device=self.device)
+            else:
+                res[k] = torch.full(shapes[k], float("nan"), dtype=self.dtype, device=self.device)
+        for k, v in res.items():
+            want = torch.int32 if k == "n_contacts" else self.dtype
+            if tuple(v.shape) != shapes[k] or v.dtype != want or not v.is_contiguous():
+                raise ValueError(f"output {k}: need a contiguous {want} tensor of shape {shapes[k]}")
+        t = capi.SimTrialArgsC()
+        a = t.sim
+        a.n_rollouts, a.n_steps, a.n_t = B, n_steps, self.n_t
+        a.precision = self.precision
+        a.params = self.params
+        a.body, a.seed, a.tsi = self.body.data_ptr(), self.seed.data_ptr(), self.tsi.data_ptr()
+        a.q_tab, a.dq_tab, a.tau_tab = self.tables.q.data_ptr(), self.tables.dq.data_ptr(), self.tables.tau.data_ptr()
+        for k in shapes:
+            setattr(a, k, res[k].data_ptr() if k in res else None)
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        a.stream = st.cuda_stream
+        t.open_loop = 1 if open_loop else 0
+        t.torque_limit = float(torque_limit)
+        t.kick_every = int(kick_every)
+        t.kick_phase = int(kick_every) - 1 if kick_phase is None else int(kick_phase)
+        if kick_dv is not None:
+            dv = torch.as_tensor(kick_dv, dtype=self.dtype, device=self.device).contiguous()
+            if tuple(dv.shape) != (B, 3):
+                raise ValueError(f"kick_dv: need [B][3] = {(B, 3)}, got {tuple(dv.shape)}")
+            self._kick_dv = dv  # alive until the launch has run
+            t.kick_dv = dv.data_ptr()
+        t.hc = float(hc)
+        t.check_from, t.check_until = int(check_from), int(check_until)
+        t.state, t.fall_z = self.state.data_ptr(), self.fall_z.data_ptr()
+        capi.check(capi.load().hs_sim_trial(self.model.handle, ctypes.byref(t)), "hs_sim_trial")
+        res["state"], res["fall_z"] = self.state, self.fall_z
+        return res
+
+    def trial_reset(self) -> None:
+        """Every rollout RUNNING again (after reset())."""
+        if hasattr(self, "state"):
+            self.state.fill_(capi.HS_TRIAL_RUNNING)
+            self.fall_z.fill_(float("nan"))
+
+    def trial_summary(self, stream=None) -> dict:
+        """hs_sim_trial_summary of ``self.state``: counts, and the minimum (-1: none) and sum of the fall tsi."""
+        torch = self.torch
+        if not hasattr(self, "state"):
+            raise capi.HSError("trial_summary: no trial has run")
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        o = capi.TrialSummaryC()
+        capi.check(capi.load().hs_sim_trial_summary(self.state.data_ptr(), self.B, ctypes.byref(o), st.cuda_stream),
+                   "hs_sim_trial_summary")
+        return {k: int(getattr(o, k)) for k in ("running", "survived", "fallen", "min_fall_tsi", "sum_fall_tsi")}
+
 
 class MixedBatch(DeviceBatch):
     """Mixed-topology batch (BASELINE configs[4]): rollout b runs models[model_index[b]]

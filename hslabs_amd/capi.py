@@ -12,7 +12,7 @@ import os
 
 from . import build as _build
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 HS_OK = 0
 HS_FLAG_RANK_RETRY = 1
@@ -39,7 +39,8 @@ EXPORTS = [
     "hs_run_mixed", "hs_run_mixed_steps", "hs_run_mixed_calls", "hs_run_host", "hs_best_key_cot", "hs_best_key_encode",
     "hs_best_key_decode", "hs_last_error", "hs_abi_version",
     "hs_sim_default_params", "hs_sim_reset", "hs_sim_step", "hs_sim_create", "hs_sim_advance", "hs_sim_get_state",
-    "hs_sim_free", "hs_batch_create", "hs_batch_set_params", "hs_batch_run", "hs_batch_run_device", "hs_select_best",
+    "hs_sim_free", "hs_sim_trial", "hs_sim_trial_summary", "hs_sim_set_trial", "hs_sim_get_trial_state",
+    "hs_batch_create", "hs_batch_set_params", "hs_batch_run", "hs_batch_run_device", "hs_select_best",
     "hs_batch_best_key_device", "hs_batch_free", "hs_comm_unique_id", "hs_comm_init", "hs_comm_free", "hs_comm_size",
     "hs_comm_reduce_best", "hs_select_best_comm", "hs_pergen_rec", "hs_pergen_rec_host", "hs_model_lik",
     "hs_model_lik_host", "hs_model_fk", "hs_model_fk_host", "hs_model_get_node", "hs_model_set_torso_penalty",
@@ -47,6 +48,8 @@ EXPORTS = [
 ]
 HS_FLAG_LIK_FAILED = 128
 SIM_BODY_STRIDE = 13
+HS_TRIAL_RUNNING = -1
+HS_TRIAL_SURVIVED = -2
 
 
 class GaitParamsC(ctypes.Structure):
@@ -124,6 +127,21 @@ class SimArgsC(ctypes.Structure):
                 ("precision", ctypes.c_int32), ("params", SimParamsC)] + \
                [(f, ctypes.c_void_p) for f in ("body", "seed", "tsi", "q_tab", "dq_tab", "tau_tab", "tau_cmd", "q_meas",
                                                "torso", "n_contacts", "normal_force", "stream")]
+
+
+class SimTrialArgsC(ctypes.Structure):
+    """hs_sim_trial_args."""
+    _fields_ = [("sim", SimArgsC)] + \
+               [(f, ctypes.c_int32) for f in ("open_loop", "kick_every", "kick_phase", "check_from", "check_until",
+                                              "reserved")] + \
+               [("torque_limit", ctypes.c_double), ("hc", ctypes.c_double), ("kick_dv", ctypes.c_void_p),
+                ("state", ctypes.c_void_p), ("fall_z", ctypes.c_void_p)]
+
+
+class TrialSummaryC(ctypes.Structure):
+    """hs_trial_summary."""
+    _fields_ = [("running", ctypes.c_int32), ("survived", ctypes.c_int32), ("fallen", ctypes.c_int32),
+                ("min_fall_tsi", ctypes.c_int32), ("sum_fall_tsi", ctypes.c_int64)]
 
 
 class HSError(RuntimeError):
@@ -218,6 +236,11 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
     L.hs_sim_advance.argtypes = [vp, ctypes.c_int32, dp, dp, dp, ctypes.POINTER(ctypes.c_int32), dp]
     L.hs_sim_get_state.argtypes = [vp, dp, ctypes.POINTER(ctypes.c_int32)]
     L.hs_sim_free.argtypes = [vp]
+    L.hs_sim_trial.argtypes = [vp, ctypes.POINTER(SimTrialArgsC)]
+    L.hs_sim_trial_summary.argtypes = [vp, ctypes.c_int32, ctypes.POINTER(TrialSummaryC), vp]
+    L.hs_sim_set_trial.argtypes = [vp, ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_int32, dp,
+                                   ctypes.c_double, ctypes.c_int32, ctypes.c_int32]
+    L.hs_sim_get_trial_state.argtypes = [vp, ctypes.POINTER(ctypes.c_int32)]
     L.hs_sim_free.restype = None
     L.hs_batch_create.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint32,
                                   ctypes.POINTER(vp)]

@@ -1273,11 +1273,17 @@ int hs_sim_reset(hs_model_t m, int32_t n_rollouts, const double* config, int32_t
   return HS_OK;
 }
 
-int hs_sim_step(hs_model_t m, const hs_sim_args* a) {
+// the checks hs_sim_step and hs_sim_trial share; *nothing = 1 for an empty call. open_loop reads
+// the torque table whatever k is.
+static int sim_args_check(hs_model_t m, const hs_sim_args* a, bool open_loop, bool* nothing) {
+  *nothing = false;
   if (!m || !a) return fail(HS_E_ARG, "null model or args");
   if (a->n_rollouts < 0 || a->n_rollouts > (1 << 30)) return fail(HS_E_ARG, "bad n_rollouts");
   if (a->n_steps < 0) return fail(HS_E_ARG, "n_steps < 0");
-  if (a->n_rollouts == 0 || a->n_steps == 0) return HS_OK;
+  if (a->n_rollouts == 0 || a->n_steps == 0) {
+    *nothing = true;
+    return HS_OK;
+  }
   if (!a->body || !a->seed || !a->tsi) return fail(HS_E_ARG, "body, seed and tsi are required");
   const hs_sim_params& P = a->params;
   if (!(P.dt > 0)) return fail(HS_E_ARG, "dt must be > 0");
@@ -1287,17 +1293,76 @@ int hs_sim_step(hs_model_t m, const hs_sim_args* a) {
     if (a->n_t < 1) return fail(HS_E_ARG, "n_t must be >= 1 with position control");
     if (!a->q_tab || !a->dq_tab || !a->tau_tab) return fail(HS_E_ARG, "controller tables are required when k > 0");
   }
+  if (open_loop) {
+    if (a->n_t < 1) return fail(HS_E_ARG, "n_t must be >= 1 with open-loop torques");
+    if (!a->tau_tab) return fail(HS_E_ARG, "the torque table is required with open_loop");
+  }
   if (m->sim.m_max > 9 * HS_NMAX) return fail(HS_E_TOPOLOGY, "too many constraint rows for the simulation kernel");
   if (a->precision != HS_PREC_F64 && a->precision != HS_PREC_F32) return fail(HS_E_ARG, "unknown precision");
+  return HS_OK;
+}
+
+int hs_sim_step(hs_model_t m, const hs_sim_args* a) {
+  bool nothing = false;
+  int rc = sim_args_check(m, a, false, &nothing);
+  if (rc != HS_OK || nothing) return rc;
   const hs_topo* d = nullptr;
   const hs_simtopo* ds = nullptr;
   const hs_simtopo_t<float>* dsf = nullptr;
-  int rc = sim_device_state(m, &d, &ds, a->precision == HS_PREC_F32 ? &dsf : nullptr);
+  rc = sim_device_state(m, &d, &ds, a->precision == HS_PREC_F32 ? &dsf : nullptr);
   if (rc != HS_OK) return rc;
   hs_sim_args c = *a;
   if (c.n_t < 1) c.n_t = 1;
   int e = hs::launch_sim_steps(d, ds, dsf, m->sim, c);
   if (e != 0) return hip_fail((hipError_t)e, "hs_sim_step launch");
+  return HS_OK;
+}
+
+int hs_sim_trial(hs_model_t m, const hs_sim_trial_args* t) {
+  if (!t) return fail(HS_E_ARG, "null model or args");
+  const hs_sim_args* a = &t->sim;
+  bool nothing = false;
+  int rc = sim_args_check(m, a, t->open_loop != 0, &nothing);
+  if (rc != HS_OK) return rc;
+  if (!(t->torque_limit >= 0)) return fail(HS_E_ARG, "torque_limit must be >= 0 (0: no limit)");
+  if (t->kick_every > 0) {
+    if (t->kick_phase < 0 || t->kick_phase >= t->kick_every)
+      return fail(HS_E_ARG, "kick_phase must lie in [0, kick_every)");
+    if (!t->kick_dv) return fail(HS_E_ARG, "kick_dv is required when kick_every > 0");
+  }
+  if (nothing) return HS_OK;
+  if (!t->state) return fail(HS_E_ARG, "the trial state array is required");
+  const hs_topo* d = nullptr;
+  const hs_simtopo* ds = nullptr;
+  const hs_simtopo_t<float>* dsf = nullptr;
+  rc = sim_device_state(m, &d, &ds, a->precision == HS_PREC_F32 ? &dsf : nullptr);
+  if (rc != HS_OK) return rc;
+  hs_sim_trial_args c = *t;
+  if (c.sim.n_t < 1) c.sim.n_t = 1;
+  if (!c.kick_dv) c.kick_every = 0;  // NULL means no kicks
+  int e = hs::launch_sim_trial(d, ds, dsf, m->sim, c);
+  if (e != 0) return hip_fail((hipError_t)e, "hs_sim_trial launch");
+  return HS_OK;
+}
+
+int hs_sim_trial_summary(const int32_t* state, int32_t n, hs_trial_summary* out, void* stream) {
+  if (!out || n < 0 || (n > 0 && !state)) return fail(HS_E_ARG, "hs_sim_trial_summary: null state or output, or n < 0");
+  hs_trial_summary acc;
+  memset(&acc, 0, sizeof(acc));
+  acc.min_fall_tsi = INT32_MAX;
+  if (n > 0) {
+    hipStream_t st = (hipStream_t)stream;
+    hs_trial_summary* dacc = nullptr;
+    hipError_t e = hipMalloc((void**)&dacc, sizeof(acc));
+    if (e == hipSuccess) e = hipMemcpyAsync(dacc, &acc, sizeof(acc), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = (hipError_t)hs::launch_trial_summary(state, n, dacc, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(&acc, dacc, sizeof(acc), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (dacc) (void)hipFree(dacc);
+    if (e != hipSuccess) return hip_fail(e, "hs_sim_trial_summary");
+  }
+  if (acc.fallen == 0) acc.min_fall_tsi = -1;
+  *out = acc;
   return HS_OK;
 }
 
@@ -1310,6 +1375,10 @@ struct hs_sim_s {
   void *params_d, *q, *dq, *tau, *body, *seed, *tsi;
   void* out[5];
   size_t out_steps;
+  // hs_sim_set_trial: the settings (device pointers filled in per call), trial_on = hs_sim_advance runs them
+  bool trial_on;
+  hs_sim_trial_args trial;
+  void *kick_dv, *state;
 };
 
 void hs_sim_free(hs_sim_t s) {
@@ -1318,7 +1387,7 @@ void hs_sim_free(hs_sim_t s) {
   (void)hipGetDevice(&cur);
   (void)hipSetDevice(s->dev);
   if (s->stream) (void)hipStreamSynchronize(s->stream);
-  for (void* p : {s->params_d, s->q, s->dq, s->tau, s->body, s->seed, s->tsi}) (void)hipFree(p);
+  for (void* p : {s->params_d, s->q, s->dq, s->tau, s->body, s->seed, s->tsi, s->kick_dv, s->state}) (void)hipFree(p);
   for (void* p : s->out) (void)hipFree(p);
   if (s->stream) (void)hipStreamDestroy(s->stream);
   (void)hipSetDevice(cur);
@@ -1433,12 +1502,65 @@ int hs_sim_advance(hs_sim_t s, int32_t n_steps, double* tau_cmd, double* q_meas,
   a.n_contacts = n_contacts ? (int32_t*)s->out[3] : nullptr;
   a.normal_force = normal_force ? (double*)s->out[4] : nullptr;
   a.stream = s->stream;
-  int rc = hs_sim_step(s->model, &a);
+  int rc;
+  if (s->trial_on) {
+    hs_sim_trial_args t = s->trial;
+    t.sim = a;
+    t.kick_dv = (const double*)s->kick_dv;
+    t.state = (int32_t*)s->state;
+    t.fall_z = nullptr;
+    // a frozen rollout leaves its remaining rows unwritten: the host sees zeros there
+    for (int i = 0; i < 5 && e == hipSuccess; i++)
+      if (host[i]) e = hipMemsetAsync(s->out[i], 0, bytes[i], s->stream);
+    if (e != hipSuccess) return hip_fail(e, "hs_sim_advance");
+    rc = hs_sim_trial(s->model, &t);
+  } else {
+    rc = hs_sim_step(s->model, &a);
+  }
   if (rc != HS_OK) return rc;
   for (int i = 0; i < 5 && e == hipSuccess; i++)
     if (host[i]) e = hipMemcpyAsync(host[i], s->out[i], bytes[i], hipMemcpyDeviceToHost, s->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
   if (e != hipSuccess) return hip_fail(e, "hs_sim_advance");
+  return HS_OK;
+}
+
+int hs_sim_set_trial(hs_sim_t s, int32_t open_loop, double torque_limit, int32_t kick_every, int32_t kick_phase,
+                     const double* kick_dv_host, double hc, int32_t check_from, int32_t check_until) {
+  if (!s) return fail(HS_E_ARG, "null sim");
+  if (!(torque_limit >= 0)) return fail(HS_E_ARG, "torque_limit must be >= 0 (0: no limit)");
+  if (kick_every > 0 && kick_dv_host && (kick_phase < 0 || kick_phase >= kick_every))
+    return fail(HS_E_ARG, "kick_phase must lie in [0, kick_every)");
+  const size_t nb = (size_t)s->B;
+  hipError_t e = hipSetDevice(s->dev);
+  if (e == hipSuccess && !s->state) e = hipMalloc(&s->state, nb * sizeof(int32_t));
+  if (e == hipSuccess && kick_dv_host && !s->kick_dv) e = hipMalloc(&s->kick_dv, nb * 3 * sizeof(double));
+  if (e == hipSuccess && kick_dv_host)
+    e = hipMemcpyAsync(s->kick_dv, kick_dv_host, nb * 3 * sizeof(double), hipMemcpyHostToDevice, s->stream);
+  std::vector<int32_t> run(nb, HS_TRIAL_RUNNING);
+  if (e == hipSuccess) e = hipMemcpyAsync(s->state, run.data(), nb * sizeof(int32_t), hipMemcpyHostToDevice, s->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+  if (e != hipSuccess) return hip_fail(e, "hs_sim_set_trial");
+  memset(&s->trial, 0, sizeof(s->trial));
+  s->trial.open_loop = open_loop;
+  s->trial.torque_limit = torque_limit;
+  s->trial.kick_every = kick_dv_host ? kick_every : 0;
+  s->trial.kick_phase = kick_phase;
+  s->trial.hc = hc;
+  s->trial.check_from = check_from;
+  s->trial.check_until = check_until;
+  s->trial_on = true;
+  return HS_OK;
+}
+
+int hs_sim_get_trial_state(hs_sim_t s, int32_t* state_host) {
+  if (!s || !state_host) return fail(HS_E_ARG, "null sim or state");
+  if (!s->trial_on) return fail(HS_E_ARG, "hs_sim_set_trial first");
+  hipError_t e = hipSetDevice(s->dev);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(state_host, s->state, (size_t)s->B * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+  if (e != hipSuccess) return hip_fail(e, "hs_sim_get_trial_state");
   return HS_OK;
 }
 

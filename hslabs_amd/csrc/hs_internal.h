@@ -132,6 +132,13 @@ int launch_sim_reset(const hs_topo* d_topo, const hs_simtopo* d_sim, int32_t n_r
                      int32_t config_stride, double* body, int32_t precision, void* stream);
 int launch_sim_steps(const hs_topo* d_topo, const hs_simtopo* d_sim, const hs_simtopo_t<float>* d_sim_f32,
                      const hs_simtopo& host_sim, const hs_sim_args& a);
+// the TRIAL instantiations of the same kernel (hs_sim_trial), and the tally of a state array into
+// acc = {running, survived, fallen, min fall tsi (INT32_MAX: none), sum fall tsi}, preset by the caller
+int launch_sim_trial(const hs_topo* d_topo, const hs_simtopo* d_sim, const hs_simtopo_t<float>* d_sim_f32,
+                     const hs_simtopo& host_sim, const hs_sim_trial_args& a);
+int launch_trial_summary(const int32_t* state, int32_t n, hs_trial_summary* acc, void* stream);
+// resident rollouts per CU of hs_sim_step's kernels for a model size: {fp64, fp32, fp32 3 waves/SIMD}
+int sim_step_occupancy(int32_t n, int32_t m_max, int32_t* out3);
 
 }  // namespace hs
 

@@ -41,6 +41,15 @@
 #include "hs_math.h"
 #include "hs_ode.h"
 
+// hs_sim_trial.hip compiles this file again with HS_SIM_TRIAL_TU for the TRIAL instantiations of the
+// kernel: in one translation unit with the plain ones they change the code the compiler emits for
+// the plain fp64 kernels (23 commuted operands; measured 1 % on hs_sim_step), apart they cannot.
+#ifdef HS_SIM_TRIAL_TU
+#define HS_SIM_TU_TRIAL true
+#else
+#define HS_SIM_TU_TRIAL false
+#endif
+
 namespace {
 
 using namespace hsode;
@@ -386,14 +395,50 @@ __device__ inline int run_row(const L& s, int se, int pair) {  // row of a lane 
 // MINW: waves per SIMD the register budget is built for. 1 leaves every kernel its 256 VGPRs
 // (2 waves/SIMD); the fp32 kernel also exists at 3 (168 VGPRs, 32 B of spills), which fits 11
 // instead of 8 rollouts per CU but runs each ~20 % slower (launch_class picks per batch).
-template <int NM, int MM, class Real, int MINW>
+//
+// TRIAL: the fall test's instantiations (hs_sim_trial). They take hs_sim_trial_args and add the
+// pieces simulate_ode (player.cpp:326-340) runs around the QuickStep: open-loop torques
+// (playerexperim.cpp:143-148), clip_torque (player.cpp:753-762), kick_torso (player.cpp:585-605) and
+// fall_check (player.cpp:669-681), which here freezes the rollout and ends its wavefront. Every
+// addition sits under `if constexpr (TRIAL)` or a `TRIAL &&` the front end folds: the TRIAL = false
+// instantiations (hs_sim_step) read hs_sim_args alone and take no new branch (Trials,
+// compares their instructions with the kernel before the parameter existed).
+template <bool TRIAL>
+struct SimKA { using type = hs_sim_args; };
+template <>
+struct SimKA<true> { using type = hs_sim_trial_args; };
+__host__ __device__ inline const hs_sim_args& sim_of(const hs_sim_args& a) { return a; }
+__host__ __device__ inline const hs_sim_args& sim_of(const hs_sim_trial_args& a) { return a.sim; }
+__device__ inline constexpr bool open_loop_of(const hs_sim_args&) { return false; }
+__device__ inline bool open_loop_of(const hs_sim_trial_args& a) { return a.open_loop != 0; }
+
+// a trial's registers: the kick force f = dv / play_dt (player.cpp:600), formed once, in the lane that
+// owns body 0 (zero elsewhere); whether this step kicks; the outcome, RUNNING until a fall check
+// freezes the rollout, and the height that check saw. Nothing in a plain instantiation.
+template <class real, bool TRIAL>
+struct TrialRegs {
+  real kf[3] = {0, 0, 0};
+  bool kick = false;
+  int state = HS_TRIAL_RUNNING;
+  real z = 0;
+};
+template <class real>
+struct TrialRegs<real, false> {};
+
+template <int NM, int MM, class Real, int MINW, bool TRIAL>
 __global__ __launch_bounds__(WAVE, MINW) void hs_sim_kernel(const hs_topo* __restrict__ T0,
-                                                         const hs_simtopo_t<Real>* __restrict__ S, hs_sim_args a) {
+                                                         const hs_simtopo_t<Real>* __restrict__ S,
+                                                         typename SimKA<TRIAL>::type ka) {
   using real = Real;
   __shared__ SimL<NM, MM, Real> s;
+  const hs_sim_args& a = sim_of(ka);
   const int lane = threadIdx.x;
   const int b = blockIdx.x;
   if (b >= a.n_rollouts) return;
+  // a rollout that enters the launch frozen does nothing (wave-uniform: one rollout per wavefront)
+  if constexpr (TRIAL) {
+    if (ka.state[b] != HS_TRIAL_RUNNING) return;
+  }
   const hs_simtopo_t<Real>& T = *S;
   const int n = T.n, nmj = T.nmj, nj = T.nj, cfg = T0->cfg;
   const SimP<real> P(a.params);
@@ -425,15 +470,47 @@ __global__ __launch_bounds__(WAVE, MINW) void hs_sim_kernel(const hs_topo* __res
   if (lane < n) s.invm[lane] = real(1) / T.mass[lane];
   wave_sync();
 
+  TrialRegs<real, TRIAL> tr;
+  if constexpr (TRIAL) {
+    if (ka.kick_every > 0 && lane == 0) {
+      const real* dv = reinterpret_cast<const real*>(ka.kick_dv) + (size_t)b * 3;
+      for (int i = 0; i < 3; i++) tr.kf[i] = dv[i] / h;
+    }
+  }
   SIM_ACC(0);
   for (int step = 0; step < a.n_steps; step++) {
     const size_t orow = (size_t)b * a.n_steps + step;
+    if constexpr (TRIAL) {
+      // ---- fall_check (player.cpp:669-681) before the step: s.pos[0][2] is an LDS broadcast, so the
+      // whole wave takes the same branch and leaves through the tail that stores the world
+      if (tsi >= ka.check_from) {
+        if (ka.check_until >= 0 && tsi > ka.check_until) {
+          tr.state = HS_TRIAL_SURVIVED;
+          tr.z = s.pos[0][2];
+          break;
+        }
+        const real z = s.pos[0][2];
+        if (z < (real)ka.hc) {
+          tr.state = tsi;
+          tr.z = z;
+          break;
+        }
+      }
+      tr.kick = ka.kick_every > 0 && tsi % ka.kick_every == ka.kick_phase;  // kick_torso (player.cpp:589)
+    }
     // ---- P: position control (set_position_control_torques, player.cpp:388-409)
     if (lane < nmj) {
       const hs_simjoint_t<real>& J = T.joint[T.motor_joint[lane]];
       const real qm = hinge_angle(s, J);
       real tq = 0;
-      if (P.k > 0) {
+      if constexpr (TRIAL) {
+        if (ka.open_loop != 0) {  // set_open_loop_torques (playerexperim.cpp:143-148): the table row alone
+          const int t = tsi % a.n_t;
+          const int hrow = (t + a.n_t - 2) % a.n_t;
+          tq = tau_tab[((size_t)b * a.n_t + hrow) * nmj + lane];
+        }
+      }
+      if (P.k > 0 && !(TRIAL && open_loop_of(ka))) {
         real ax[3], R1[12];
         q_to_R(s.q[J.b1], R1);
         mul0_331(ax, R1, J.axis1);
@@ -450,6 +527,11 @@ __global__ __launch_bounds__(WAVE, MINW) void hs_sim_kernel(const hs_topo* __res
         a1 += a2;
         tq = tau_tab[tb * nmj + lane] + a1;
       }
+      if constexpr (TRIAL) {
+        // clip_torque (player.cpp:753-762), the reference's expression; applied and recorded clipped
+        const real lim = (real)ka.torque_limit;
+        if (lim > 0 && fabs(tq) > lim) tq = lim * tq / fabs(tq);
+      }
       s.tau[lane] = tq;
       if (o_q) o_q[orow * nmj + lane] = qm;
       if (o_tau) o_tau[orow * nmj + lane] = tq;
@@ -460,7 +542,7 @@ __global__ __launch_bounds__(WAVE, MINW) void hs_sim_kernel(const hs_topo* __res
     if (lane < n) {
       const int p = lane;
       real tq[3] = {0, 0, 0};
-      if (P.k > 0) {
+      if (P.k > 0 || (TRIAL && open_loop_of(ka))) {  // open loop applies its torques whatever k is
         for (int c = 0; c < T.tq_n[p]; c++) {  // dJointAddHingeTorque in motor order
           const int j = T.tq_motor[p][c];
           const hs_simjoint_t<real>& J = T.joint[T.motor_joint[j]];
@@ -525,6 +607,11 @@ __global__ __launch_bounds__(WAVE, MINW) void hs_sim_kernel(const hs_topo* __res
       tq[1] -= w[2] * t3[0] - w[0] * t3[2];
       tq[2] -= w[0] * t3[1] - w[1] * t3[0];
       real fa[3] = {0, 0, 0};
+      if constexpr (TRIAL) {
+        // dBodyAddForce before the stepper (visualization.cpp:406-411); gravity goes on top
+        if (tr.kick)
+          for (int i = 0; i < 3; i++) fa[i] = tr.kf[i];
+      }
       if (P.gravity != 0) fa[2] += T.mass[p] * (-P.gravity);
       const real im = s.invm[p];
       for (int i = 0; i < 3; i++) {
@@ -774,6 +861,10 @@ __global__ __launch_bounds__(WAVE, MINW) void hs_sim_kernel(const hs_topo* __res
       for (int j = 0; j < 3; j++) s.avel[p][j] += h * s.fc[p][3 + j];
       const real hm = h * s.invm[p];
       real fa[3] = {0, 0, 0};  // facc: gravity only (the motors add torques)
+      if constexpr (TRIAL) {
+        if (tr.kick)  // ... and the step's kick on the root body, the same facc as above
+          for (int i = 0; i < 3; i++) fa[i] = tr.kf[i];
+      }
       if (P.gravity != 0) fa[2] += T.mass[p] * (-P.gravity);
       real ta[3];
       for (int j = 0; j < 3; j++) {
@@ -826,9 +917,53 @@ __global__ __launch_bounds__(WAVE, MINW) void hs_sim_kernel(const hs_topo* __res
   if (lane == 0) {
     a.seed[b] = s.seed;
     a.tsi[b] = tsi;
+    if constexpr (TRIAL) {
+      if (tr.state != HS_TRIAL_RUNNING) {
+        ka.state[b] = tr.state;
+        if (ka.fall_z) reinterpret_cast<real*>(ka.fall_z)[b] = tr.z;
+      }
+    }
   }
 }
 
+#ifdef HS_SIM_TRIAL_TU
+// Tally of a trial state array: grid-stride loop, cross-lane reduction per wavefront, one atomic
+// per wavefront and counter. acc->min_fall_tsi starts at INT32_MAX, the rest at 0.
+__global__ __launch_bounds__(256) void hs_trial_summary_kernel(const int32_t* __restrict__ state, int32_t n,
+                                                                hs_trial_summary* __restrict__ acc) {
+  int running = 0, survived = 0, fallen = 0, mn = INT32_MAX;
+  long long sum = 0;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const int st = state[i];
+    if (st == HS_TRIAL_RUNNING) running++;
+    else if (st == HS_TRIAL_SURVIVED) survived++;
+    else {
+      fallen++;
+      mn = min(mn, st);
+      sum += st;
+    }
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    running += __shfl_xor(running, off);
+    survived += __shfl_xor(survived, off);
+    fallen += __shfl_xor(fallen, off);
+    mn = min(mn, __shfl_xor(mn, off));
+    sum += __shfl_xor(sum, off);
+  }
+  if ((threadIdx.x & (WAVE - 1)) == 0) {
+    if (running) atomicAdd(&acc->running, running);
+    if (survived) atomicAdd(&acc->survived, survived);
+    if (fallen) {
+      atomicAdd(&acc->fallen, fallen);
+      atomicMin(&acc->min_fall_tsi, mn);
+      atomicAdd(reinterpret_cast<unsigned long long*>(&acc->sum_fall_tsi), (unsigned long long)sum);
+    }
+  }
+}
+#endif
+
+#ifndef HS_SIM_TRIAL_TU
 // init_play_config + orient_odebodys: lane = part, A_ground by walking the chain from the root
 // (each product in the reference's order: J_A_ground = A_parent J_A_parent, then * E(q) * A_pj_body).
 // IO = the precision of the configuration and body arrays; the pose is built in double and
@@ -872,10 +1007,11 @@ __global__ __launch_bounds__(WAVE) void hs_sim_reset_kernel(const hs_topo* __res
   for (int i = 7; i < 13; i++) o[i] = 0;
   (void)R;
 }
+#endif
 
 }  // namespace
 
-#ifdef HS_SIM_STAMPS
+#if defined(HS_SIM_STAMPS) && !defined(HS_SIM_TRIAL_TU)
 extern "C" int hs_debug_read_sim_stamps(unsigned long long* out, int n_rows) {
   if (n_rows > 4096) n_rows = 4096;
   return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_sim_stamps), sizeof(unsigned long long) * 16 * n_rows, 0,
@@ -889,6 +1025,7 @@ extern "C" int hs_debug_clear_sim_stamps() {
 
 namespace hs {
 
+#ifndef HS_SIM_TRIAL_TU
 int launch_sim_reset(const hs_topo* d_topo, const hs_simtopo* d_sim, int32_t n_rollouts, const double* config,
                      int32_t config_stride, double* body, int32_t precision, void* stream) {
   if (n_rollouts <= 0) return 0;
@@ -901,52 +1038,118 @@ int launch_sim_reset(const hs_topo* d_topo, const hs_simtopo* d_sim, int32_t n_r
                        config, config_stride, body);
   return (int)hipGetLastError();
 }
+#endif
+
+// resident rollouts per CU of kernel k (the occupancy query; <= 0: unknown)
+static int sim_per_cu(const void* k) {
+  int per_cu = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, WAVE, 0) != hipSuccess) return -1;
+  return per_cu;
+}
 
 // rounds of resident rollouts a batch needs with kernel k (every rollout runs a whole launch)
 static long sim_rounds(const void* k, long B) {
-  int per_cu = 0, dev = 0, cus = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, WAVE, 0) != hipSuccess || per_cu <= 0) return -1;
+  int dev = 0, cus = 0;
+  const int per_cu = sim_per_cu(k);
+  if (per_cu <= 0) return -1;
   if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
     return -1;
   const long slots = (long)per_cu * cus;
   return (B + slots - 1) / slots;
 }
 
-template <int NM, int MM, class R, class S>
-static void launch_class(const hs_topo* d_topo, const S* d_sim, const hs_sim_args& a, hipStream_t st) {
+// the fp64 trial kernel is held to the 2-waves/SIMD budget the plain one meets on its own (with a free
+// budget it takes 255 VGPRs + 4 AGPRs, one wave per SIMD, and loses a third of its rollouts per CU)
+template <class R, bool TRIAL>
+constexpr int sim_minw() { return (TRIAL && sizeof(R) == 8) ? 2 : 1; }
+
+template <int NM, int MM, class R, bool TRIAL, class S>
+static void launch_class(const hs_topo* d_topo, const S* d_sim, const typename SimKA<TRIAL>::type& ka, hipStream_t st) {
+  const hs_sim_args& a = sim_of(ka);
   if constexpr (sizeof(R) == 4) {
     // the 3-waves/SIMD build when it saves more than its per-rollout slowdown in rounds
     // (measured: spider B = 16384, 8 -> 6 rounds, +8 %; hexapod B = 4096, 2 -> 2 rounds, -9 %)
-    const long r2 = sim_rounds((const void*)hs_sim_kernel<NM, MM, R, 1>, a.n_rollouts);
-    const long r3 = sim_rounds((const void*)hs_sim_kernel<NM, MM, R, 3>, a.n_rollouts);
+    const long r2 = sim_rounds((const void*)hs_sim_kernel<NM, MM, R, 1, TRIAL>, a.n_rollouts);
+    const long r3 = sim_rounds((const void*)hs_sim_kernel<NM, MM, R, 3, TRIAL>, a.n_rollouts);
     if (r2 > 0 && r3 > 0 && 5 * r3 < 4 * r2) {
-      hipLaunchKernelGGL((hs_sim_kernel<NM, MM, R, 3>), dim3(a.n_rollouts), dim3(WAVE), 0, st, d_topo, d_sim, a);
+      hipLaunchKernelGGL((hs_sim_kernel<NM, MM, R, 3, TRIAL>), dim3(a.n_rollouts), dim3(WAVE), 0, st, d_topo, d_sim, ka);
       return;
     }
   }
-  hipLaunchKernelGGL((hs_sim_kernel<NM, MM, R, 1>), dim3(a.n_rollouts), dim3(WAVE), 0, st, d_topo, d_sim, a);
+  hipLaunchKernelGGL((hs_sim_kernel<NM, MM, R, sim_minw<R, TRIAL>(), TRIAL>), dim3(a.n_rollouts), dim3(WAVE), 0, st,
+                     d_topo, d_sim, ka);
 }
 
-template <class R, class S>
-static int launch_sim_typed(const hs_topo* d_topo, const S* d_sim, const hs_simtopo& hs, const hs_sim_args& a) {
-  hipStream_t st = (hipStream_t)a.stream;
+template <class R, bool TRIAL, class S>
+static int launch_sim_typed(const hs_topo* d_topo, const S* d_sim, const hs_simtopo& hs,
+                            const typename SimKA<TRIAL>::type& ka) {
+  hipStream_t st = (hipStream_t)sim_of(ka).stream;
   // smallest LDS layout holding the model: parts and rows (6 per fixed, 5 per hinge, 3 per contact)
   if (hs.n <= 18 && hs.m_max <= 144)
-    launch_class<18, 144, R>(d_topo, d_sim, a, st);
+    launch_class<18, 144, R, TRIAL>(d_topo, d_sim, ka, st);
   else if (hs.n <= 22 && hs.m_max <= 176)
-    launch_class<22, 176, R>(d_topo, d_sim, a, st);
+    launch_class<22, 176, R, TRIAL>(d_topo, d_sim, ka, st);
   else if (hs.n <= HS_NMAX && hs.m_max <= 9 * HS_NMAX)
-    launch_class<HS_NMAX, 9 * HS_NMAX, R>(d_topo, d_sim, a, st);
+    launch_class<HS_NMAX, 9 * HS_NMAX, R, TRIAL>(d_topo, d_sim, ka, st);
   else
     return (int)hipErrorInvalidValue;
   return (int)hipGetLastError();
 }
 
+// rollouts per CU of this translation unit's instantiations of one LDS class: {fp64, fp32, fp32 3 waves/SIMD}
+template <int NM, int MM>
+static void class_occupancy(int32_t* out) {
+  constexpr bool T = HS_SIM_TU_TRIAL;
+  out[0] = sim_per_cu((const void*)hs_sim_kernel<NM, MM, double, sim_minw<double, T>(), T>);
+  out[1] = sim_per_cu((const void*)hs_sim_kernel<NM, MM, float, 1, T>);
+  out[2] = sim_per_cu((const void*)hs_sim_kernel<NM, MM, float, 3, T>);
+}
+static int tu_occupancy(int32_t n, int32_t m_max, int32_t* out3) {
+  if (n <= 18 && m_max <= 144) class_occupancy<18, 144>(out3);
+  else if (n <= 22 && m_max <= 176) class_occupancy<22, 176>(out3);
+  else if (n <= HS_NMAX && m_max <= 9 * HS_NMAX) class_occupancy<HS_NMAX, 9 * HS_NMAX>(out3);
+  else return -1;
+  return 0;
+}
+
+#ifndef HS_SIM_TRIAL_TU
 int launch_sim_steps(const hs_topo* d_topo, const hs_simtopo* d_sim, const hs_simtopo_t<float>* d_sim_f32,
                      const hs_simtopo& hs, const hs_sim_args& a) {
   if (a.n_rollouts <= 0 || a.n_steps <= 0) return 0;
-  if (a.precision == HS_PREC_F32) return launch_sim_typed<float>(d_topo, d_sim_f32, hs, a);
-  return launch_sim_typed<double>(d_topo, d_sim, hs, a);
+  if (a.precision == HS_PREC_F32) return launch_sim_typed<float, false>(d_topo, d_sim_f32, hs, a);
+  return launch_sim_typed<double, false>(d_topo, d_sim, hs, a);
 }
 
+int sim_step_occupancy(int32_t n, int32_t m_max, int32_t* out3) { return tu_occupancy(n, m_max, out3); }
+#else
+int launch_sim_trial(const hs_topo* d_topo, const hs_simtopo* d_sim, const hs_simtopo_t<float>* d_sim_f32,
+                     const hs_simtopo& hs, const hs_sim_trial_args& a) {
+  if (a.sim.n_rollouts <= 0 || a.sim.n_steps <= 0) return 0;
+  if (a.sim.precision == HS_PREC_F32) return launch_sim_typed<float, true>(d_topo, d_sim_f32, hs, a);
+  return launch_sim_typed<double, true>(d_topo, d_sim, hs, a);
+}
+
+int launch_trial_summary(const int32_t* state, int32_t n, hs_trial_summary* acc, void* stream) {
+  if (n <= 0) return 0;
+  const int blocks = (int)((((long)n + 255) / 256 < 1024) ? ((long)n + 255) / 256 : 1024);
+  hipLaunchKernelGGL(hs_trial_summary_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, state, n, acc);
+  return (int)hipGetLastError();
+}
+#endif
+
 }  // namespace hs
+
+#ifdef HS_SIM_TRIAL_TU
+// Diagnostic (tools/fall_test.py --occupancy; not part of hslabs.h): resident rollouts per CU of the
+// simulation kernel's instantiations for a model of n parts and m_max rows, as
+// {fp64, fp64 trial, fp32, fp32 trial, fp32 3 waves/SIMD, fp32 3 waves/SIMD trial}.
+extern "C" int hs_debug_sim_occupancy(int32_t n, int32_t m_max, int32_t* out6) {
+  int32_t plain[3], trial[3];
+  if (hs::sim_step_occupancy(n, m_max, plain) != 0 || hs::tu_occupancy(n, m_max, trial) != 0) return -1;
+  for (int i = 0; i < 3; i++) {
+    out6[2 * i] = plain[i];
+    out6[2 * i + 1] = trial[i];
+  }
+  return 0;
+}
+#endif

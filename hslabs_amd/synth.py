@@ -94,3 +94,19 @@ def gen_sim_params(n: int, model: str = "hexapod", id0: int = 0, period: float =
     arr = gen_params(n, model, id0, False, seed)
     arr["period"] = period
     return arr
+
+
+def gen_kicks(B: int, lo: float, hi: float, plane: str = "xz", seed: int = SEED, id0: int = 0) -> np.ndarray:
+    """Torso kicks [B][3] for SimBatch.trial(kick_dv=...): the velocity change's magnitude uniform in
+    [lo, hi], its direction uniform in the plane. "xz" is the plane of the reference's (commented-out)
+    random draw, dvx = kick cos(th), dvz = kick sin(th) (kick_torso, player.cpp:590-595); "xy" is
+    horizontal. Streams 6 (magnitude) and 7 (angle) of the rollout's counter."""
+    if plane not in ("xz", "xy"):
+        raise ValueError(f"plane must be 'xz' or 'xy', got {plane!r}")
+    ids = np.arange(id0, id0 + B, dtype=np.int64)
+    mag = uniform(ids, 6, lo, hi, seed)
+    th = uniform(ids, 7, 0.0, 2.0 * np.pi, seed)
+    dv = np.zeros((B, 3))
+    dv[:, 0] = mag * np.cos(th)
+    dv[:, 2 if plane == "xz" else 1] = mag * np.sin(th)
+    return dv

@@ -19,7 +19,7 @@
 extern "C" {
 #endif
 
-#define HSLABS_ABI_VERSION 15
+#define HSLABS_ABI_VERSION 16
 
 enum {
   HS_OK = 0,
@@ -522,6 +522,63 @@ typedef struct {
 /* n_steps closed-loop steps of every rollout, one launch (state stays on chip between steps). */
 int hs_sim_step(hs_model_t model, const hs_sim_args* args);
 
+/*
+ * Batched fall test (ABI 16): the flagged pieces modelplayer::simulate_ode (player.cpp:326-340)
+ * runs around the QuickStep besides position control, per rollout, in hs_sim_step's launch shape.
+ * One trial step, in simulate_ode's order:
+ *   torque law: open_loop != 0 -> tau = tau_tab[row(tsi)], no feedback, whatever k is
+ *     (set_open_loop_torques, playerexperim.cpp:143-148); else the PD law of hs_sim_step (k > 0).
+ *     q_meas is written either way;
+ *   torque limit (torque_limit > 0): where |tau| > limit, tau = limit * tau / |tau|
+ *     (clip_torque, player.cpp:753-762), before the torques are applied; tau_cmd records the clipped
+ *     value (set_ode_motor_torques clips, applies, then saves: player.cpp:740-745);
+ *   kick (kick_every > 0 and tsi % kick_every == kick_phase): the force f = kick_dv[b] / dt on the root
+ *     body for this step (kick_torso, player.cpp:585-605: dBodyAddForce before the stepper,
+ *     visualization.cpp:406-411; gravity is added on top). The reference's live values are
+ *     kick_every 500, kick_phase 499, dv (4, 0, 0). Deviation: the reference tests
+ *     int(play_t / play_dt) of an accumulated double, this library its integer tsi;
+ *   fall check (fall_check, player.cpp:669-681), before the step: nothing while tsi < check_from;
+ *     tsi > check_until (check_until >= 0) -> survived ("No fall by t"); else root pos[2] < hc ->
+ *     fallen at this tsi ("Fall at t"). Instead of exit(1) the rollout is frozen: the step is not
+ *     taken, body / seed / tsi stay as they are, its remaining per-step output rows are not
+ *     written, and its wavefront ends (the slot goes to the next rollout of the grid). A rollout
+ *     that enters a launch frozen does nothing;
+ *   otherwise the step of hs_sim_step.
+ */
+#define HS_TRIAL_RUNNING (-1)
+#define HS_TRIAL_SURVIVED (-2)
+
+typedef struct {
+  hs_sim_args sim;         /* as for hs_sim_step */
+  int32_t open_loop;       /* != 0: feed-forward torques only */
+  int32_t kick_every;      /* <= 0: no kicks */
+  int32_t kick_phase;      /* in [0, kick_every) */
+  int32_t check_from;      /* first tsi at which the fall check runs */
+  int32_t check_until;     /* last tsi at which a fall counts; < 0: never "survived" */
+  int32_t reserved;
+  double torque_limit;     /* 0: no limit */
+  double hc;               /* fall height of the root body */
+  const double* kick_dv;   /* DEVICE [B][3] velocity change per kick; NULL = no kicks; floats with HS_PREC_F32 */
+  int32_t* state;          /* DEVICE [B], read and advanced: HS_TRIAL_RUNNING, HS_TRIAL_SURVIVED, else the
+                              tsi at which the rollout fell */
+  double* fall_z;          /* DEVICE [B], optional: the height seen by the check that froze the rollout
+                              (floats with HS_PREC_F32) */
+} hs_sim_trial_args;
+
+/* n_steps trial steps of every rollout, one launch. HS_E_ARG for a NULL state, kick_every > 0 with
+ * kick_phase outside [0, kick_every) or a NULL kick_dv, torque_limit < 0, open_loop without tables,
+ * and everything hs_sim_step rejects. */
+int hs_sim_trial(hs_model_t model, const hs_sim_trial_args* args);
+
+typedef struct {
+  int32_t running, survived, fallen;
+  int32_t min_fall_tsi;    /* -1 when nothing fell */
+  int64_t sum_fall_tsi;
+} hs_trial_summary;
+
+/* Tally of state [n] (DEVICE) into *out_host (HOST); one reduction launch on stream, synchronous. */
+int hs_sim_trial_summary(const int32_t* state, int32_t n, hs_trial_summary* out_host, void* stream);
+
 /* Host-side handle over the calls above, for callers without device memory of their own
  * (the C++ shim's modelplayer): owns the device tables and state of B rollouts.
  * hs_sim_create = modelplayer::setup_per_controller (player.cpp:370-382) for every rollout:
@@ -536,6 +593,13 @@ int hs_sim_advance(hs_sim_t sim, int32_t n_steps, double* tau_cmd, double* q_mea
                    double* normal_force);
 /* HOST copies of the state: body [B][n_parts][HS_SIM_BODY_STRIDE], tsi [B] (either may be NULL). */
 int hs_sim_get_state(hs_sim_t sim, double* body, int32_t* tsi);
+/* The handle's trial settings (hs_sim_trial_args; kick_dv_host: HOST [B][3] or NULL = no kicks). Every
+ * rollout's state becomes HS_TRIAL_RUNNING, and hs_sim_advance runs hs_sim_trial from now on. A handle
+ * on which this was never called runs hs_sim_step. */
+int hs_sim_set_trial(hs_sim_t sim, int32_t open_loop, double torque_limit, int32_t kick_every, int32_t kick_phase,
+                     const double* kick_dv_host, double hc, int32_t check_from, int32_t check_until);
+/* HOST copy of the trial state [B] (HS_E_ARG before hs_sim_set_trial). */
+int hs_sim_get_trial_state(hs_sim_t sim, int32_t* state_host);
 void hs_sim_free(hs_sim_t sim);
 
 /* The fused step launches' kernel (ABI 15). hs_run_calls takes the limb-lane kernel (lane = (rollout,

@@ -743,6 +743,43 @@ class modelplayer {
   double play_t_ = 0, play_dt_ = 0.01;
   std::string traj_fname_ = "traj.txt";
   std::vector<double> last_tau_, last_q_;
+  // the flagged pieces of simulate_ode (player.cpp:326-340) besides position control
+  bool open_loop_flag_ = false, torso_kicks_flag_ = false, clip_torque_flag_ = false, fall_check_flag_ = false;
+  double torque_limit_ = 0, fall_hc_ = 0, fall_tmin_ = 0, fall_tmax_ = 1e10;  // player.cpp:29-30
+  double kick_dv_[3] = {4, 0, 0};       // kick_torso's live values (player.cpp:588-595)
+  int kick_every_ = 500, kick_phase_ = 499;
+  bool trial_dirty_ = true, trial_set_ = false;
+  int fall_state_ = HS_TRIAL_RUNNING;
+
+  bool any_trial_flag() const { return open_loop_flag_ || torso_kicks_flag_ || clip_torque_flag_ || fall_check_flag_; }
+  // first tsi whose tsi * dt is not < tmin, last tsi whose tsi * dt is not > tmax (fall_check's comparisons,
+  // player.cpp:670, on tsi * play_dt instead of the accumulated play_t)
+  int first_tsi_at(double tmin) const {
+    if (!(tmin > 0)) return 0;
+    int i = std::max(0, (int)std::min(tmin / play_dt_, 2.0e9) - 2);
+    while (i * play_dt_ < tmin) i++;
+    return i;
+  }
+  int last_tsi_at(double tmax) const {
+    if (tmax / play_dt_ >= 2.0e9) return -1;  // never "No fall by t" within int32 steps
+    if (tmax < 0) return 0;                   // tsi = 0 is checked as fallen-or-not, anything later survives
+    int i = (int)(tmax / play_dt_) + 2;
+    while (i > 0 && i * play_dt_ > tmax) i--;
+    return i;
+  }
+  void push_trial() {
+    const bool on = any_trial_flag();
+    if (!on && !trial_set_) return;  // never armed: hs_sim_advance stays on hs_sim_step
+    // flags switched off again: the trial path with every extra off is hs_sim_step's arithmetic
+    check(hs_sim_set_trial(sim_, open_loop_flag_ ? 1 : 0, clip_torque_flag_ ? torque_limit_ : 0.0,
+                           torso_kicks_flag_ ? kick_every_ : 0, kick_phase_, torso_kicks_flag_ ? kick_dv_ : nullptr,
+                           fall_hc_, fall_check_flag_ ? first_tsi_at(fall_tmin_) : INT32_MAX,
+                           fall_check_flag_ ? last_tsi_at(fall_tmax_) : -1),
+          "hs_sim_set_trial");
+    trial_set_ = true;
+    trial_dirty_ = false;
+    fall_state_ = HS_TRIAL_RUNNING;
+  }
 
  public:
   modelplayer() {}
@@ -761,20 +798,81 @@ class modelplayer {
     play_t_ = int(t0 / play_dt_ + .5) * play_dt_;
     last_tau_.assign(model_.number_of_motor_joints(), 0);
     last_q_.assign(model_.number_of_motor_joints(), 0);
+    trial_dirty_ = true;
+    trial_set_ = false;
+    fall_state_ = HS_TRIAL_RUNNING;
   }
   void unset_per_controller() {
     if (sim_) hs_sim_free(sim_);
     sim_ = nullptr;
+  }
+  // playerexperim.cpp:134-140 without the draw loop: the world set up with the open-loop flag on; call
+  // simulate_ode(n), then unset_per_controller() and set_flag("open_loop", false) as the reference does
+  void open_loop_test(const pergensetup* pgs, double t0) {
+    set_flag("open_loop", true);
+    setup_per_controller(pgs, t0);
   }
   // player.cpp:325-339 (position control): PD torques, dJointAddHingeTorque, collide, QuickStep
   void simulate_ode(int n_steps = 1) {
     if (!sim_) throw error(HS_E_ARG, "setup_per_controller first");
     const int nmj = model_.number_of_motor_joints();
     std::vector<double> tau((size_t)n_steps * nmj), q((size_t)n_steps * nmj);
+    if (trial_dirty_) push_trial();
+    if (!trial_set_) {
+      check(hs_sim_advance(sim_, n_steps, tau.data(), q.data(), nullptr, nullptr, nullptr), "simulate_ode");
+      std::copy(tau.end() - nmj, tau.end(), last_tau_.begin());
+      std::copy(q.end() - nmj, q.end(), last_q_.begin());
+      play_t_ += n_steps * play_dt_;
+      return;
+    }
+    // the trial path: a fallen or survived world is frozen, so play_t follows the steps taken
+    int32_t tsi0 = 0, tsi1 = 0;
+    check(hs_sim_get_state(sim_, nullptr, &tsi0), "simulate_ode");
     check(hs_sim_advance(sim_, n_steps, tau.data(), q.data(), nullptr, nullptr, nullptr), "simulate_ode");
-    std::copy(tau.end() - nmj, tau.end(), last_tau_.begin());
-    std::copy(q.end() - nmj, q.end(), last_q_.begin());
-    play_t_ += n_steps * play_dt_;
+    check(hs_sim_get_state(sim_, nullptr, &tsi1), "simulate_ode");
+    int32_t st = HS_TRIAL_RUNNING;
+    check(hs_sim_get_trial_state(sim_, &st), "simulate_ode");
+    fall_state_ = st;
+    const int taken = tsi1 - tsi0;
+    if (taken > 0) {
+      std::copy(tau.begin() + (size_t)(taken - 1) * nmj, tau.begin() + (size_t)taken * nmj, last_tau_.begin());
+      std::copy(q.begin() + (size_t)(taken - 1) * nmj, q.begin() + (size_t)taken * nmj, last_q_.begin());
+    }
+    play_t_ += taken * play_dt_;
+  }
+  // fall_check's verdict (player.cpp:669-681) instead of exit(1): fallen ("Fall at t = "), survived
+  // ("No fall by t = ") or neither yet, and the play time of that check
+  struct fall_result {
+    bool fallen, survived;
+    double t;
+  };
+  fall_result fall_state() const {
+    if (fall_state_ == HS_TRIAL_RUNNING) return {false, false, play_t_};
+    if (fall_state_ == HS_TRIAL_SURVIVED) return {false, true, play_t_};
+    return {true, false, fall_state_ * play_dt_};
+  }
+  // player.cpp:747-750
+  void set_torque_limit(double torque) {
+    if (!(torque >= 0)) throw error(HS_E_ARG, "torque limit must be >= 0");
+    torque_limit_ = torque;
+    set_flag("clip_torque", true);
+  }
+  // player.cpp:779-786 (speedup_draw and ignore_reach have no counterpart: nothing is drawn, and
+  // setup_per_controller's tables already ignore reach)
+  void set_fall_test(double hc, double tmin, double tmax) {
+    fall_hc_ = hc;
+    fall_tmin_ = tmin;
+    fall_tmax_ = tmax;
+    set_flag("fall_check", true);
+  }
+  // the kick kick_torso hard-codes (player.cpp:588-595): velocity change dv every `every` steps, at
+  // int(play_t / play_dt) % every == phase
+  void set_torso_kick(const double* dv, int every = 500, int phase = 499) {
+    if (every < 1 || phase < 0 || phase >= every) throw error(HS_E_ARG, "kick phase must lie in [0, every)");
+    std::copy(dv, dv + 3, kick_dv_);
+    kick_every_ = every;
+    kick_phase_ = phase;
+    trial_dirty_ = true;
   }
   double get_play_t() const { return play_t_; }
   void set_play_dt(double dt) { play_dt_ = dt; }
@@ -804,7 +902,12 @@ class modelplayer {
   kinematicmodel* get_model() { return &model_; }
   void set_flag(const std::string& name, bool v) {
     if (name == "contact_force") contact_force_flag_ = v;
+    else if (name == "open_loop") open_loop_flag_ = v;      // player.cpp:86-87
+    else if (name == "torso_kicks") torso_kicks_flag_ = v;  // player.cpp:104-105
+    else if (name == "clip_torque") clip_torque_flag_ = v;  // player.cpp:108-109
+    else if (name == "fall_check") fall_check_flag_ = v;    // player.cpp:110-111
     else throw error(HS_E_ARG, "unknown flag " + name);
+    if (name != "contact_force") trial_dirty_ = true;
   }
   // player.cpp:147-166
   pergensetup* make_pergensu(const std::string& config_fname, int setup_id, const std::string& model_dir = "") {
