@@ -47,8 +47,7 @@ void free_on_device(int dev, void* p) {
 // one rollout's workspace slot: either precision's RolloutWS (the fp32 build's general path computes
 // in double, so its slot is not simply half the fp64 one)
 static size_t ws_slot_bytes() {
-  const size_t a = hs::general_workspace_bytes(), b = hs::general_workspace_bytes_f32();
-  return a > b ? a : b;
+  return std::max(hs::kernels_f64.general_workspace_bytes(), hs::kernels_f32.general_workspace_bytes());
 }
 
 int ws_pool::get(void* stream, size_t n, void** out) {
@@ -82,6 +81,23 @@ void ws_pool::release() {
   live.clear();
   retired.clear();
 }
+
+struct hs_mixed_s : run_pools {
+  int dev = 0;
+  int32_t n_rollouts = 0, n_waves = 0;
+  std::vector<hs_model_t> models;
+  hs_model_dims max_dims;
+  int32_t st_tau = 0, st_cf = 0, st_q = 0, st_x = 0;
+  hs_topo* d_topos = nullptr;  // the models' topologies, contiguous (wave_model indexes it)
+  int32_t* d_wave_model = nullptr;
+  int32_t* d_wave_rollouts = nullptr;
+  // the limb-lane kernel's layout (every model of the plan of its class): 8 rollouts of one model per
+  // wavefront, [model], [8 * wave] rollout ids (-1 idle) and their hs_rollout_kernel slots
+  int32_t limb_waves = 0;
+  int32_t *d_limb_model = nullptr, *d_limb_rollouts = nullptr;
+  double* d_rollout_mass = nullptr;  // total mass of each rollout's model (the fused reduce's COT)
+  int32_t torso_mask = 3;            // 3 unless a model's switch_torso_penalty (at plan creation) differs
+};
 
 namespace {
 
@@ -141,56 +157,6 @@ int sim_device_state(hs_model_t m, const hs_topo** topo, const hs_simtopo** sim,
   return HS_OK;
 }
 
-// n_calls launches, k0 marching through the cycle (hs_run_steps semantics). total_mass / rollout_mass:
-// the model's, or a mixed plan's per-rollout masses (the best key's selection COT)
-int launch_steps(const hs_topo* d, const hs_run_args& a, void* ws, const hs::launch_map& mp, int32_t n_calls,
-                 void* const* kernel_events, double total_mass, const double* rollout_mass) {
-  hs_run_args c = a;
-  hipStream_t st = (hipStream_t)a.stream;
-  // the best key covers the work of all n_calls calls: taken after the last one only
-  if (c.key_steps == 0) c.key_steps = (int32_t)std::min<int64_t>((int64_t)n_calls * a.horizon, INT32_MAX);
-  // With the work in work_cot the key is taken by the work reduce kernel after the last launch (n_steps
-  // = 0: it re-reads the accumulated work, writes the same values back and min-reduces each workgroup's
-  // 64 keys before its one atomic): taken in the step launch, every wavefront's atomic on the one key
-  // address queued behind the others' and the call's last launch ran 26-39 us instead of 19.6 us
-  // (profiles/r05_t1_steps_trace_tail.txt, VERDICT r04 weak 5)
-  const bool key_reduce = a.best_key && a.work_cot && !mp.tau_in;
-  // one gait setup per rollout per call: the preparation pass of the fused path (hs_prep_kernel: the
-  // setup record, sample times, IK table and torso record) stores it and every launch loads it, so the
-  // kinematics of these launches and of hs_run_calls' fused launches come from the same kernels
-  hs::launch_map base = mp;
-  base.setup_only = 1;
-  base.setup_io = hs::SETUP_STORE;
-  base.fix_n_counts = 0;
-  hs::ktab_range(a.k0, a.n_t, a.horizon, n_calls, &base.ktab_lo, &base.ktab_n, &base.ttab_n);
-  const int le0 = (a.precision == HS_PREC_F32) ? hs::launch_fused_f32(d, c, ws, base) : hs::launch_fused(d, c, ws, base);
-  if (le0 != 0) return hip_fail((hipError_t)le0, "kernel launch (setup pass)");
-  base.setup_only = 0;
-  for (int32_t i = 0; i < n_calls; i++) {
-    c.k0 = (int32_t)(((int64_t)a.k0 + (int64_t)i * a.horizon) % a.n_t);
-    c.best_key = (i + 1 == n_calls && !key_reduce) ? a.best_key : nullptr;
-    hs::launch_map mi = base;
-    mi.setup_io = hs::SETUP_LOAD;
-    hipError_t e = hipSuccess;
-    if (kernel_events) e = hipEventRecord((hipEvent_t)kernel_events[2 * i], st);
-    if (e != hipSuccess) return hip_fail(e, "hipEventRecord");
-    int le = (a.precision == HS_PREC_F32) ? hs::launch_rollouts_f32(d, c, ws, mi) : hs::launch_rollouts(d, c, ws, mi);
-    if (le != 0) return hip_fail((hipError_t)le, "kernel launch");
-    if (kernel_events) e = hipEventRecord((hipEvent_t)kernel_events[2 * i + 1], st);
-    if (e != hipSuccess) return hip_fail(e, "hipEventRecord");
-  }
-  if (key_reduce) {
-    hs_run_args r = c;
-    r.best_key = a.best_key;
-    r.accumulate = 1;  // the work the launches accumulated; no step terms added
-    const int le = (a.precision == HS_PREC_F32) ? hs::launch_fused_reduce_f32(r, total_mass, rollout_mass, nullptr, 0)
-                                                : hs::launch_fused_reduce(r, total_mass, rollout_mass, nullptr, 0);
-    if (le != 0) return hip_fail((hipError_t)le, "kernel launch (best key)");
-  }
-  return HS_OK;
-}
-
-
 // switch_torso_penalty other than (1,1): the closed form solves the (1,1) problem, so every step of
 // the call takes the Eigen-style path (HS_SOLVE_REFERENCE routing, the launches sized for it)
 hs_run_args routed(const hs_run_args& a, int32_t torso_mask) {
@@ -214,50 +180,218 @@ int check_args(const hs_model_s* m, const hs_run_args* a) {
   return HS_OK;
 }
 
-// hs_run_calls / hs_run_mixed_calls: a setup-only pass, launches of CHUNK steps over (step, wavefront),
-// the in-order work reduce. Each step in flight in a launch has its own general-path scratch.
-// The limb-lane kernel (hs_limb.h) takes the fused step launches of a call when the model is of its class
-// (hs_topo::limb_lane_ok), the call solves in HS_SOLVE_AUTO and asks for no x, q or dq rows (the kernel
-// writes tau, cf, flags and the work terms), and the preparation pass holds the IK table (the kernel reads
-// its rows); HS_LIMB=0 in the environment keeps hs_rollout_kernel's fused step launch (A/B, tests)
+// What a run entry point launches with, built by model_ctx (one model) or mixed_ctx (a mixed plan) once
+// their checks pass.
+struct launch_ctx {
+  bool empty = false;               // no rollouts or no calls: nothing to launch, the fields below unset
+  const hs::kernels* k = nullptr;   // the launchers of the call's precision
+  const hs_topo* d_topo = nullptr;  // device topology (a mixed plan: its models' contiguous array)
+  void* ws = nullptr;               // the rollout workspace of (device, stream)
+  // the wavefronts' rollouts, the output strides and the samples the call's preparation pass stores
+  // (ktab_range); the entry points and the launch paths fill the rest in their copies
+  hs::launch_map map{};
+  run_pools* pools = nullptr;  // the model's or the plan's: run_fused's buffers
+  // the model's total mass, or a mixed plan's per-rollout masses (the best key's selection COT)
+  double total_mass = 0.0;
+  const double* rollout_mass = nullptr;
+  const hs_topo* host = nullptr;  // route()'s model class (a mixed plan with the limb layout: any of its models)
+  int32_t torso_mask = 3;         // routed()
+};
+
+// The checks every single-model run entry point makes, in their order: the arguments, n_calls, then the
+// entry point's own (entry_check, returning fail(...) or HS_OK); then the device topology, the workspace
+// (+ 1: the idle half-wave of an odd batch) and the model's launch map.
+template <class Check = int (*)()>
+int model_ctx(hs_model_t m, const hs_run_args* a, int32_t n_calls, launch_ctx& cx,
+              Check entry_check = [] { return (int)HS_OK; }) {
+  int rc = check_args(m, a);
+  if (rc != HS_OK) return rc;
+  if (n_calls < 0) return fail(HS_E_ARG, "n_calls < 0");
+  rc = entry_check();
+  if (rc != HS_OK) return rc;
+  cx.empty = a->n_rollouts == 0 || n_calls == 0;
+  if (cx.empty) return HS_OK;
+  rc = device_state(m, a->n_rollouts + 1, a->stream, &cx.d_topo, &cx.ws);
+  if (rc != HS_OK) return rc;
+  cx.k = &hs::kernels_of(a->precision);
+  cx.map = hs::single_model_map(m->host, a->n_rollouts);
+  hs::ktab_range(a->k0, a->n_t, a->horizon, n_calls, &cx.map.ktab_lo, &cx.map.ktab_n, &cx.map.ttab_n);
+  cx.pools = m;
+  cx.total_mass = m->host.total_mass;
+  cx.host = &m->host;
+  cx.torso_mask = m->host.torso_mask;
+  return HS_OK;
+}
+
+// The same for a mixed plan: the plan's device instead of a topology upload, its wavefront maps and,
+// when every model is of the limb-lane kernel's class, that kernel's layout.
+int mixed_ctx(hs_mixed_t p, const hs_run_args* a, int32_t n_calls, launch_ctx& cx) {
+  if (!p) return fail(HS_E_ARG, "null plan");
+  int rc = check_args(p->models[0], a);
+  if (rc != HS_OK) return rc;
+  if (a->n_rollouts != p->n_rollouts) return fail(HS_E_ARG, "n_rollouts differs from the plan's");
+  if (n_calls < 0) return fail(HS_E_ARG, "n_calls < 0");
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return hip_fail(e, "hipGetDevice");
+  if (dev != p->dev) return fail(HS_E_DEVICE, "plan was created on another device");
+  cx.empty = a->n_rollouts == 0 || n_calls == 0;
+  if (cx.empty) return HS_OK;
+  hs::launch_map& mp = cx.map;
+  mp.wave_model = p->d_wave_model;
+  mp.wave_rollouts = p->d_wave_rollouts;
+  mp.n_waves = p->n_waves;
+  mp.max_parts = p->max_dims.n_parts;
+  mp.st_tau = p->st_tau;
+  mp.st_cf = p->st_cf;
+  mp.st_q = p->st_q;
+  mp.st_x = p->st_x;
+  if (p->d_limb_model) {
+    mp.limb_model = p->d_limb_model;
+    mp.limb_rollouts = p->d_limb_rollouts;
+    mp.limb_slots = p->d_limb_rollouts + 8 * (size_t)p->limb_waves;
+    mp.limb_waves = p->limb_waves;
+  }
+  hs::ktab_range(a->k0, a->n_t, a->horizon, n_calls, &mp.ktab_lo, &mp.ktab_n, &mp.ttab_n);
+  {
+    std::lock_guard<std::mutex> lk(p->mu);
+    e = (hipError_t)p->ws.get(a->stream, (size_t)p->n_rollouts + 1, &cx.ws);
+  }
+  if (e != hipSuccess) return hip_fail(e, "hipMalloc(workspace)");
+  cx.k = &hs::kernels_of(a->precision);
+  cx.d_topo = p->d_topos;
+  cx.pools = p;
+  cx.rollout_mass = p->d_rollout_mass;
+  cx.host = &p->models[0]->host;
+  cx.torso_mask = p->torso_mask;
+  return HS_OK;
+}
+
+// A call's preparation pass (hs_prep_kernel): one gait setup per rollout, stored for every step launch,
+// the sample times, the IK table and torso record; it zeroes mp's fixup counters. Leaves mp set for the
+// step launches, which load the setup.
+int launch_setup(const launch_ctx& cx, const hs_run_args& c, hs::launch_map& mp) {
+  mp.setup_only = 1;
+  mp.setup_io = hs::SETUP_STORE;
+  const int le = cx.k->launch_fused(cx.d_topo, c, cx.ws, mp);
+  mp.setup_only = 0;
+  mp.setup_io = hs::SETUP_LOAD;
+  mp.fix_n_counts = 0;
+  return le;
+}
+
+// n_calls launches, k0 marching through the cycle (hs_run_steps semantics)
+int launch_steps(const launch_ctx& cx, const hs_run_args& a, int32_t n_calls, void* const* kernel_events) {
+  const hs::kernels& k = *cx.k;
+  hs_run_args c = a;
+  hipStream_t st = (hipStream_t)a.stream;
+  // the best key covers the work of all n_calls calls: taken after the last one only
+  if (c.key_steps == 0) c.key_steps = (int32_t)std::min<int64_t>((int64_t)n_calls * a.horizon, INT32_MAX);
+  // With the work in work_cot the key is taken by the work reduce kernel after the last launch (n_steps
+  // = 0: it re-reads the accumulated work, writes the same values back and min-reduces each workgroup's
+  // 64 keys before its one atomic): taken in the step launch, every wavefront's atomic on the one key
+  // address queued behind the others' and the call's last launch ran 26-39 us instead of 19.6 us
+  // (profiles/r05_t1_steps_trace_tail.txt, VERDICT r04 weak 5)
+  const bool key_reduce = a.best_key && a.work_cot && !cx.map.tau_in;
+  // the preparation pass of the fused path, so the kinematics of these launches and of hs_run_calls'
+  // fused launches come from the same kernels
+  hs::launch_map mp = cx.map;
+  const int le0 = launch_setup(cx, c, mp);
+  if (le0 != 0) return hip_fail((hipError_t)le0, "kernel launch (setup pass)");
+  for (int32_t i = 0; i < n_calls; i++) {
+    c.k0 = (int32_t)(((int64_t)a.k0 + (int64_t)i * a.horizon) % a.n_t);
+    c.best_key = (i + 1 == n_calls && !key_reduce) ? a.best_key : nullptr;
+    hipError_t e = hipSuccess;
+    if (kernel_events) e = hipEventRecord((hipEvent_t)kernel_events[2 * i], st);
+    if (e != hipSuccess) return hip_fail(e, "hipEventRecord");
+    int le = k.launch_rollouts(cx.d_topo, c, cx.ws, mp);
+    if (le != 0) return hip_fail((hipError_t)le, "kernel launch");
+    if (kernel_events) e = hipEventRecord((hipEvent_t)kernel_events[2 * i + 1], st);
+    if (e != hipSuccess) return hip_fail(e, "hipEventRecord");
+  }
+  if (key_reduce) {
+    hs_run_args r = c;
+    r.best_key = a.best_key;
+    r.accumulate = 1;  // the work the launches accumulated; no step terms added
+    const int le = k.launch_fused_reduce(r, cx.total_mass, cx.rollout_mass, nullptr, 0);
+    if (le != 0) return hip_fail((hipError_t)le, "kernel launch (best key)");
+  }
+  return HS_OK;
+}
+
 std::atomic<int64_t> g_limb_launches{0};
-// hs_run_steps' calls up to this horizon take the limb-lane kernel (a launch per call holds the call's
-// horizon steps; longer calls keep hs_rollout_kernel's launch)
+// hs_run_steps' calls up to this horizon take the online shapes (a launch per call holds the call's
+// horizon steps; longer calls keep hs_rollout_kernel's launch per step)
 #define HS_ONLINE_MAX_H 64
 
-bool limb_kernel_wanted() {
-  const char* e = getenv("HS_LIMB");  // read per call: a test switches kernels within one process
-  return !(e && e[0] == '0');
-}
-bool limb_online_wanted() {
-  const char* e = getenv("HS_LIMB_ONLINE");
-  return e && e[0] == '1';
-}
-bool limb_f32_wanted() {
-  const char* e = getenv("HS_LIMB_F32");
-  return !(e && e[0] == '0');
-}
-bool limb_eligible(const hs_topo& host, const hs_run_args& a) {
-  // fp32: within the single-precision build's bound of hs_rollout_kernel's float results, not bitwise
-  // (float contraction differs by context: ~1e-6 relative); HS_LIMB_F32=0 keeps hs_rollout_kernel there
-  return limb_kernel_wanted() && host.limb_lane_ok && a.solve_mode == HS_SOLVE_AUTO && !a.x && !a.q && !a.dq &&
-         (a.precision == HS_PREC_F64 || limb_f32_wanted());
+// A switch of the step kernels' routing, read from the environment on every call (a test switches kernels
+// within one process): one that is on by default is off at a value starting with 0, one that is off by
+// default is on at a value starting with 1. HS_LIMB (on), HS_LIMB_F32 (on), HS_LIMB_ONLINE (off),
+// HS_ONLINE_DEFER (off), HS_FIX_BARRIER (on).
+bool env_switch(const char* name, bool on_by_default) {
+  const char* e = getenv(name);
+  if (!e) return on_by_default;
+  return on_by_default ? e[0] != '0' : e[0] == '1';
 }
 
-// online (hs_run_steps through the limb-lane kernel): a launch per call over its horizon steps, each call
-// writing output rows [0, horizon) like hs_run_steps' launches, its declined steps fixed and its work
-// added to work_cot (in step order, the reduce's two roundings) by one fixup + reduce launch before the
-// next call's launch, the best key by the last call's reduce
-int run_fused(const hs_topo* d, const hs_run_args& a, void* ws, hs::launch_map mp, ws_pool& gen_pool,
-              ws_pool& work_pool, ws_pool& fix_pool, std::mutex& mu, double total_mass, const double* rollout_mass,
-              int32_t n_calls, bool limb = false, bool online = false, void* const* kernel_events = nullptr) {
-  const int64_t S = online ? a.horizon : (int64_t)n_calls * a.horizon;  // output rows per rollout
-  if (S > (1 << 24) || (int64_t)n_calls * a.horizon > INT32_MAX) return fail(HS_E_ARG, "too many steps");
-  // steps per launch: the launch refills the SIMDs from its queue of wavefronts (the batch's last
-  // wavefronts no longer end every step). Up to 512k wavefronts per launch (256 rounds of a full
-  // MI355X at 2 per SIMD; measured B = 4096, 200 steps, interleaved A/B: 16 steps -2.5 %, 32 steps
-  // -0.5 % against 64; 128 steps +0.5 %, 256 steps +1.2 % against 64), and each step in flight
-  // holds general-path scratch for its rollouts (~13 GB at 512k wavefronts, of 288 GB HBM).
+enum class step_route {
+  ROLLOUT,       // launch_steps: hs_rollout_kernel, a launch per step, the general path inline
+  ONLINE_DEFER,  // run_fused's online shape on hs_rollout_kernel's fused FIX_DEFER instantiation
+  LIMB_ONLINE,   // the online shape on the limb-lane kernel
+  FUSED,         // hs_rollout_kernel's fused step launches
+  LIMB_FUSED,    // the limb-lane kernel's
+};
+enum class run_entry { STEPS, CALLS, FORCES_CALLS };
+
+// Which step kernel a call takes and in which launch shape. `a`: the call's arguments after routed()
+// (FORCES_CALLS: the caller's own, that entry point does not route). The limb-lane kernel (hs_limb.h)
+// writes tau, cf, flags and the work terms from the rows of the preparation pass's IK table, and takes a
+// call when every row of its entry point's column holds:
+//
+//                              STEPS                  CALLS                     FORCES_CALLS
+//                              hs_run_steps           hs_run_calls,             hs_run_forces_calls
+//                                                     hs_run_mixed_calls
+//   HS_LIMB != 0               yes                    yes                       yes
+//   hs_topo::limb_lane_ok      yes                    yes (every model)         yes
+//   HS_SOLVE_AUTO              routed                 routed                    the caller's
+//   no q rows                  yes                    yes                       yes
+//   no x and dq rows           yes                    yes                       not asked (no x there, dq unused)
+//   precision                  fp64, and fp32 unless HS_LIMB_F32=0 (both columns)   fp64 only
+//   the call fits the IK table else ONLINE_DEFER      else FUSED (also a mixed  else FUSED
+//                                                     plan without limb layout)
+//   opt-in                     HS_LIMB_ONLINE=1       -                         -
+//
+// fp32: within the single-precision build's bound of hs_rollout_kernel's float results, not bitwise
+// (float contraction differs by context: ~1e-6 relative). hs_run_steps keeps ROLLOUT past
+// HS_ONLINE_MAX_H steps per call, and takes ONLINE_DEFER itself at HS_ONLINE_DEFER=1 and HS_SOLVE_AUTO.
+step_route route(const launch_ctx& cx, const hs_run_args& a, run_entry entry) {
+  const bool forces = entry == run_entry::FORCES_CALLS, f32 = a.precision == HS_PREC_F32;
+  const auto limb_eligible = [&] {
+    return env_switch("HS_LIMB", true) && cx.host->limb_lane_ok && a.solve_mode == HS_SOLVE_AUTO && !a.q &&
+           (forces || (!a.x && !a.dq)) && (!f32 || (!forces && env_switch("HS_LIMB_F32", true)));
+  };
+  const bool table = cx.map.ktab_n > 0 && (!cx.map.wave_rollouts || cx.map.limb_rollouts);
+  if (entry != run_entry::STEPS) return limb_eligible() && table ? step_route::LIMB_FUSED : step_route::FUSED;
+  if (a.horizon > HS_ONLINE_MAX_H) return step_route::ROLLOUT;
+  // HS_LIMB_ONLINE=1: a launch per call and a fixup + reduce launch after it (the same outputs, work and
+  // key bitwise). Not the default: its launch of B / 8 wavefronts lasts one wavefront's life, 18.2-18.7 us
+  // at B = 4096 (the limb lanes' dependent chain), and the fixup + reduce adds 4.7-5.2 us: 155 M steps/s
+  // against hs_rollout_kernel's launch per call with the general path inline, 20 us at 32 lanes per rollout
+  // (profiles/r06_t7_steps_trace_tail.txt)
+  if (env_switch("HS_LIMB_ONLINE", false) && limb_eligible())
+    return table ? step_route::LIMB_ONLINE : step_route::ONLINE_DEFER;
+  // HS_ONLINE_DEFER=1: the same online shape on hs_rollout_kernel's fused instantiation (FIX_DEFER, 4
+  // waves/SIMD, no general-path call) and its fixup + reduce per call (VERDICT r05 item 4's variant;
+  // measured, DESIGN.md section 4d)
+  if (env_switch("HS_ONLINE_DEFER", false) && a.solve_mode == HS_SOLVE_AUTO) return step_route::ONLINE_DEFER;
+  return step_route::ROLLOUT;
+}
+
+// Steps per fused launch: the launch refills the SIMDs from its queue of wavefronts (the batch's last
+// wavefronts no longer end every step). Up to 512k wavefronts per launch (256 rounds of a full
+// MI355X at 2 per SIMD; measured B = 4096, 200 steps, interleaved A/B: 16 steps -2.5 %, 32 steps
+// -0.5 % against 64; 128 steps +0.5 %, 256 steps +1.2 % against 64), and each step in flight
+// holds general-path scratch for its rollouts (~13 GB at 512k wavefronts, of 288 GB HBM).
 #ifndef HS_FUSED_WAVES
 #define HS_FUSED_WAVES 524288
 #endif
@@ -267,22 +401,51 @@ int run_fused(const hs_topo* d, const hs_run_args& a, void* ws, hs::launch_map m
 #ifndef HS_FUSED_RESERVE_STEPS
 #define HS_FUSED_RESERVE_STEPS 1024
 #endif
+int32_t fused_chunk(const hs::launch_map& mp) {
+  return std::max(1, std::min(HS_FUSED_MAX_STEPS, HS_FUSED_WAVES / std::max(1, mp.n_waves)));
+}
+
+// A call's fixup buffer: n_counts int32 counters (zeroed by the setup pass), padded to 256 B, then the
+// items a launch of `chunk` steps may append: a (local step, 2 * wavefront + half) pair per step and rollout
+size_t fix_counts_bytes(int32_t n_counts) { return ((size_t)n_counts * sizeof(int32_t) + 255) / 256 * 256; }
+size_t fix_bytes(int32_t n_counts, int32_t chunk, const hs::launch_map& mp) {
+  return fix_counts_bytes(n_counts) + (size_t)chunk * mp.n_waves * 2 * 2 * sizeof(int32_t);
+}
+void fix_carve(void* fix, int32_t n_counts, hs::launch_map& mp) {
+  mp.fix_count = (int32_t*)fix;
+  mp.fix_n_counts = n_counts;
+  mp.fix_items = (int32_t*)((char*)fix + fix_counts_bytes(n_counts));
+}
+
+// hs_run_calls / hs_run_mixed_calls: a setup-only pass, launches of CHUNK steps over (step, wavefront),
+// the in-order work reduce. Each step in flight in a launch has its own general-path scratch. The step
+// launches are hs_rollout_kernel's fused instantiation or the limb-lane kernel's (route()).
+// online (hs_run_steps, route()'s two online shapes): a launch per call over its horizon steps, each call
+// writing output rows [0, horizon) like hs_run_steps' launches, its declined steps fixed and its work
+// added to work_cot (in step order, the reduce's two roundings) by one fixup + reduce launch before the
+// next call's launch, the best key by the last call's reduce
+int run_fused(const launch_ctx& cx, const hs_run_args& a, int32_t n_calls, step_route rt,
+              void* const* kernel_events = nullptr) {
+  const bool online = rt == step_route::ONLINE_DEFER || rt == step_route::LIMB_ONLINE;
+  const bool limb = rt == step_route::LIMB_ONLINE || rt == step_route::LIMB_FUSED;
+  const hs::kernels& k = *cx.k;
+  hs::launch_map mp = cx.map;
+  const int64_t S = online ? a.horizon : (int64_t)n_calls * a.horizon;  // output rows per rollout
+  if (S > (1 << 24) || (int64_t)n_calls * a.horizon > INT32_MAX) return fail(HS_E_ARG, "too many steps");
   const int32_t B = a.n_rollouts;
-  const int32_t CHUNK = online ? a.horizon
-                               : std::max(1, std::min(HS_FUSED_MAX_STEPS, HS_FUSED_WAVES / std::max(1, mp.n_waves)));
+  const int32_t CHUNK = online ? a.horizon : fused_chunk(mp);
   const int32_t n_chunks = online ? n_calls : (int32_t)((S + CHUNK - 1) / CHUNK);
   const size_t gwb = ws_slot_bytes();
   // steps the closed form declines (every step in HS_SOLVE_REFERENCE) are deferred to a fixup launch
   // after each step launch, so the step kernel carries no call to the general path; one counter per
-  // launch (zeroed by the setup pass), then the items
-  // (then as many grid-barrier counters for the fixup + reduce launches, hs_internal.h fix_barrier)
-  const size_t fix_counts_bytes = ((size_t)2 * n_chunks * sizeof(int32_t) + 255) / 256 * 256;
-  const size_t fix_bytes = fix_counts_bytes + (size_t)CHUNK * mp.n_waves * 2 * 2 * sizeof(int32_t);
+  // launch, then as many grid-barrier counters for the fixup + reduce launches (hs_internal.h
+  // fix_barrier)
+  const int32_t n_counts = 2 * n_chunks;
   void *gen = nullptr, *work = nullptr, *fix = nullptr;
   {
-    std::lock_guard<std::mutex> lk(mu);
+    std::lock_guard<std::mutex> lk(cx.pools->mu);
     // the general-path scratch of every step in flight: [CHUNK][B + 1] SolveWS (in workspace units)
-    hipError_t e = (hipError_t)gen_pool.get(
+    hipError_t e = (hipError_t)cx.pools->fused_gen.get(
         a.stream, ((size_t)CHUNK * (B + 1) * hs::solve_workspace_bytes() + gwb - 1) / gwb, &gen);
     // the [step][rollout] work buffer is reserved for at least HS_FUSED_RESERVE_STEPS steps (at most
     // 512 MB) on first use, so a caller growing its call length (a short warmup, then the real run)
@@ -290,13 +453,12 @@ int run_fused(const hs_topo* d, const hs_run_args& a, void* ws, hs::launch_map m
     const size_t need = (size_t)S * B * sizeof(double);
     const size_t want =
         std::max(need, std::min((size_t)HS_FUSED_RESERVE_STEPS * B * sizeof(double), (size_t)512 << 20));
-    if (e == hipSuccess) e = (hipError_t)work_pool.get(a.stream, (want + gwb - 1) / gwb, &work);
-    if (e == hipSuccess) e = (hipError_t)fix_pool.get(a.stream, (fix_bytes + gwb - 1) / gwb, &fix);
+    if (e == hipSuccess) e = (hipError_t)cx.pools->fused_work.get(a.stream, (want + gwb - 1) / gwb, &work);
+    if (e == hipSuccess)
+      e = (hipError_t)cx.pools->fused_fix.get(a.stream, (fix_bytes(n_counts, CHUNK, mp) + gwb - 1) / gwb, &fix);
     if (e != hipSuccess) return hip_fail(e, "hipMalloc(fused workspace)");
   }
   int32_t* fix_counts = (int32_t*)fix;
-  int32_t* fix_items = (int32_t*)((char*)fix + fix_counts_bytes);
-  const bool f32 = a.precision == HS_PREC_F32;
   hs_run_args c = a;
   c.horizon = (int32_t)S;  // output rows per rollout
   c.best_key = nullptr;    // taken by the reduce, after the last step
@@ -305,86 +467,46 @@ int run_fused(const hs_topo* d, const hs_run_args& a, void* ws, hs::launch_map m
   mp.fused_h = a.horizon;
   mp.fused_work = work;
   mp.fused_gen = gen;
-  mp.setup_only = 1;  // gait setup once per rollout, stored for every step
-  mp.setup_io = hs::SETUP_STORE;
-  mp.fix_count = fix_counts;
-  mp.fix_n_counts = 2 * n_chunks;  // the fixup counters and the barrier counters
+  fix_carve(fix, n_counts, mp);
   // the fixup + reduce launch's grid barrier: its ceil(B / 64) workgroups must be resident together
-  const char* fb = getenv("HS_FIX_BARRIER");  // 0: each workgroup fixes its own rollouts' items (A/B)
-  const bool barrier_ok = (B + 63) / 64 <= 1024 && !(fb && fb[0] == '0');
-  hs::ktab_range(a.k0, a.n_t, a.horizon, n_calls, &mp.ktab_lo, &mp.ktab_n, &mp.ttab_n);  // the preparation pass's rows
-  limb = limb && mp.ktab_n > 0 && (!mp.wave_rollouts || mp.limb_rollouts);
+  // (HS_FIX_BARRIER=0: each workgroup fixes its own rollouts' items, A/B)
+  const bool barrier_ok = (B + 63) / 64 <= 1024 && env_switch("HS_FIX_BARRIER", true);
   mp.prep_unit = limb ? 8 : 2;  // the rollouts' records written on the XCD whose step launches read them
-  int le = f32 ? hs::launch_fused_f32(d, c, ws, mp) : hs::launch_fused(d, c, ws, mp);
-  mp.setup_only = 0;
-  mp.setup_io = hs::SETUP_LOAD;
-  mp.fix_n_counts = 0;
-  mp.fix_items = fix_items;
-  bool reduced = false;
-  if (online) {
-    hipStream_t st = (hipStream_t)a.stream;
-    for (int32_t i = 0; le == 0 && i < n_calls; i++) {
-      c.k0 = (int32_t)(((int64_t)a.k0 + (int64_t)i * a.horizon) % a.n_t);
-      mp.fused_s0 = 0;
-      mp.fused_n = a.horizon;
-      mp.fix_mode = hs::FIX_DEFER;
-      mp.fix_count = fix_counts + i;
-      mp.fix_reduce = 0;
-      hipError_t e = kernel_events ? hipEventRecord((hipEvent_t)kernel_events[2 * i], st) : hipSuccess;
-      if (e != hipSuccess) return hip_fail(e, "hipEventRecord");
-      if (limb) {  // (no IK table for the call: hs_rollout_kernel's fused step launch, the same shape)
-        le = f32 ? hs::launch_limb_f32(d, c, ws, mp) : hs::launch_limb(d, c, ws, mp);
-        g_limb_launches++;
-      } else {
-        le = f32 ? hs::launch_fused_f32(d, c, ws, mp) : hs::launch_fused(d, c, ws, mp);
-      }
-      if (le != 0) break;
-      mp.fix_mode = hs::FIX_SOLVE;
-      mp.fix_reduce = a.work_cot != nullptr;
-      mp.fix_barrier = barrier_ok ? fix_counts + n_chunks + i : nullptr;
-      if (mp.fix_reduce) {
-        mp.red_total_mass = total_mass;
-        mp.red_rollout_mass = rollout_mass;
-        mp.red_n_steps = a.horizon;
-        mp.red_key_steps = r.key_steps;
-        mp.red_best_key = i + 1 == n_calls ? r.best_key : nullptr;
-      }
-      le = f32 ? hs::launch_fused_f32(d, c, ws, mp) : hs::launch_fused(d, c, ws, mp);
-      if (le == 0 && kernel_events) e = hipEventRecord((hipEvent_t)kernel_events[2 * i + 1], st);
-      if (e != hipSuccess) return hip_fail(e, "hipEventRecord");
-    }
-    if (le != 0) return hip_fail((hipError_t)le, "kernel launch");
-    return HS_OK;
-  }
-  for (int64_t s0 = 0, ci = 0; le == 0 && s0 < S; s0 += CHUNK, ci++) {
+  // the step launch (LIMB_ONLINE without the IK table is routed to hs_rollout_kernel's, the same shape)
+  const auto launch_step = limb ? k.launch_limb : k.launch_fused;
+  int le = launch_setup(cx, c, mp);
+  mp.red_total_mass = cx.total_mass;  // read by the launches with fix_reduce
+  mp.red_rollout_mass = cx.rollout_mass;
+  mp.red_key_steps = r.key_steps;
+  hipStream_t st = (hipStream_t)a.stream;
+  for (int32_t i = 0; le == 0 && i < n_chunks; i++) {  // online: call i, rows [0, S); else the i-th CHUNK steps of the S
+    const int64_t s0 = online ? 0 : (int64_t)i * CHUNK;
+    const bool last = i + 1 == n_chunks;
+    if (online) c.k0 = (int32_t)(((int64_t)a.k0 + (int64_t)i * a.horizon) % a.n_t);
     mp.fused_s0 = (int32_t)s0;
     mp.fused_n = (int32_t)std::min<int64_t>(CHUNK, S - s0);
     mp.fix_mode = hs::FIX_DEFER;
-    mp.fix_count = fix_counts + ci;
-    if (limb) {
-      le = f32 ? hs::launch_limb_f32(d, c, ws, mp) : hs::launch_limb(d, c, ws, mp);
-      g_limb_launches++;
-    }
-    else le = f32 ? hs::launch_fused_f32(d, c, ws, mp) : hs::launch_fused(d, c, ws, mp);
+    mp.fix_count = fix_counts + i;
+    mp.fix_reduce = 0;
+    hipError_t e = kernel_events ? hipEventRecord((hipEvent_t)kernel_events[2 * i], st) : hipSuccess;
+    if (e != hipSuccess) return hip_fail(e, "hipEventRecord");
+    le = launch_step(cx.d_topo, c, cx.ws, mp);
+    g_limb_launches += limb;
     if (le != 0) break;
-    // the same steps' declined (step, rollout) items, with the general path; after the last step
-    // launch of an HS_SOLVE_AUTO call (few items, if any) together with the work reduce
+    // the same steps' declined (step, rollout) items, with the general path; together with the work
+    // reduce after every online call, else after the last step launch of an HS_SOLVE_AUTO call (few
+    // items, if any)
     mp.fix_mode = hs::FIX_SOLVE;
-    mp.fix_reduce = s0 + CHUNK >= S && a.solve_mode == HS_SOLVE_AUTO && a.work_cot;
-    mp.fix_barrier = barrier_ok ? fix_counts + n_chunks + ci : nullptr;
-    if (mp.fix_reduce) {
-      mp.red_total_mass = total_mass;
-      mp.red_rollout_mass = rollout_mass;
-      mp.red_n_steps = (int32_t)S;
-      mp.red_key_steps = r.key_steps;
-      mp.red_best_key = r.best_key;
-      reduced = true;
-    }
-    le = f32 ? hs::launch_fused_f32(d, c, ws, mp) : hs::launch_fused(d, c, ws, mp);
+    mp.fix_reduce = a.work_cot && a.solve_mode == HS_SOLVE_AUTO && (online || last);
+    mp.fix_barrier = barrier_ok ? fix_counts + n_chunks + i : nullptr;
+    mp.red_n_steps = (int32_t)S;
+    mp.red_best_key = last ? r.best_key : nullptr;
+    le = k.launch_fused(cx.d_topo, c, cx.ws, mp);
+    if (le == 0 && kernel_events) e = hipEventRecord((hipEvent_t)kernel_events[2 * i + 1], st);
+    if (e != hipSuccess) return hip_fail(e, "hipEventRecord");
   }
-  if (le == 0 && !reduced)
-    le = f32 ? hs::launch_fused_reduce_f32(r, total_mass, rollout_mass, work, (int32_t)S)
-             : hs::launch_fused_reduce(r, total_mass, rollout_mass, work, (int32_t)S);
+  // HS_SOLVE_REFERENCE (or no work_cot, a no-op): the reduce was not part of the last fixup
+  if (le == 0 && !mp.fix_reduce) le = k.launch_fused_reduce(r, cx.total_mass, cx.rollout_mass, work, (int32_t)S);
   if (le != 0) return hip_fail((hipError_t)le, "kernel launch");
   return HS_OK;
 }
@@ -407,26 +529,6 @@ launch_map single_model_map(const hs_topo& t, int32_t n_rollouts) {
 
 }  // namespace hs
 
-struct hs_mixed_s {
-  int dev = 0;
-  int32_t n_rollouts = 0, n_waves = 0;
-  std::vector<hs_model_t> models;
-  hs_model_dims max_dims;
-  int32_t st_tau = 0, st_cf = 0, st_q = 0, st_x = 0;
-  hs_topo* d_topos = nullptr;  // the models' topologies, contiguous (wave_model indexes it)
-  int32_t* d_wave_model = nullptr;
-  int32_t* d_wave_rollouts = nullptr;
-  // the limb-lane kernel's layout (every model of the plan of its class): 8 rollouts of one model per
-  // wavefront, [model], [8 * wave] rollout ids (-1 idle) and their hs_rollout_kernel slots
-  int32_t limb_waves = 0;
-  int32_t *d_limb_model = nullptr, *d_limb_rollouts = nullptr;
-  double* d_rollout_mass = nullptr;  // total mass of each rollout's model (the fused reduce's COT)
-  int32_t torso_mask = 3;            // 3 unless a model's switch_torso_penalty (at plan creation) differs
-  ws_pool ws;
-  ws_pool fused_gen, fused_work, fused_fix;
-  std::mutex mu;
-};
-
 extern "C" {
 
 int hs_abi_version(void) { return HSLABS_ABI_VERSION; }
@@ -439,17 +541,14 @@ int hs_model_limb_lane(hs_model_t m, int32_t* ok) {
 
 int64_t hs_limb_launches(void) { return g_limb_launches.load(); }
 
-extern "C" int hs_limb_deferred_f64(unsigned long long* out);
-extern "C" int hs_limb_deferred_f32(unsigned long long* out);
-
 int hs_limb_stats(int64_t* launches, int64_t* deferred) {
   if (launches) *launches = g_limb_launches.load();
   if (deferred) {
-    unsigned long long a = 0, b = 0;
-    hipError_t e = (hipError_t)hs_limb_deferred_f64(&a);
-    if (e == hipSuccess) e = (hipError_t)hs_limb_deferred_f32(&b);
+    unsigned long long n[2] = {0, 0};
+    hipError_t e = (hipError_t)hs::kernels_f64.limb_deferred(&n[0]);
+    if (e == hipSuccess) e = (hipError_t)hs::kernels_f32.limb_deferred(&n[1]);
     if (e != hipSuccess) return hip_fail(e, "hs_limb_stats");
-    *deferred = (int64_t)(a + b);
+    *deferred = (int64_t)(n[0] + n[1]);
   }
   return HS_OK;
 }
@@ -481,10 +580,7 @@ void hs_model_free(hs_model_t m) {
     if (m->sim_dev[d]) free_on_device(d, m->sim_dev[d]);
     if (m->sim_dev_f32[d]) free_on_device(d, m->sim_dev_f32[d]);
   }
-  m->ws.release();
-  m->fused_gen.release();
-  m->fused_work.release();
-  m->fused_fix.release();
+  m->release();
   delete m;
 }
 
@@ -571,60 +667,33 @@ int hs_pgs_config_read(const char* path, int setup_id, hs_gait_params* out, char
 int hs_run(hs_model_t m, const hs_run_args* a) { return hs_run_steps(m, a, 1, nullptr); }
 
 int hs_run_steps(hs_model_t m, const hs_run_args* a, int32_t n_calls, void* const* kernel_events) {
-  int rc = check_args(m, a);
-  if (rc != HS_OK) return rc;
-  if (n_calls < 0) return fail(HS_E_ARG, "n_calls < 0");
-  if (a->n_rollouts == 0 || n_calls == 0) return HS_OK;
-  const hs_topo* d = nullptr;
-  void* ws = nullptr;
-  rc = device_state(m, a->n_rollouts + 1, a->stream, &d, &ws);  // + the idle half-wave of an odd batch
-  if (rc != HS_OK) return rc;
-  const hs_run_args r = routed(*a, m->host.torso_mask);
-  // HS_LIMB_ONLINE=1, the limb-lane kernel's class: a launch per call and a fixup + reduce launch after it
-  // (run_fused's online shape, the same outputs, work and key bitwise). Not the default: its launch of
-  // B / 8 wavefronts lasts one wavefront's life, 18.2-18.7 us at B = 4096 (the limb lanes' dependent
-  // chain), and the fixup + reduce adds 4.7-5.2 us: 155 M steps/s against hs_rollout_kernel's launch per
-  // call with the general path inline, 20 us at 32 lanes per rollout (profiles/r06_t7_steps_trace_tail.txt)
-  if (limb_online_wanted() && limb_eligible(m->host, r) && a->horizon <= HS_ONLINE_MAX_H)
-    return run_fused(d, r, ws, hs::single_model_map(m->host, a->n_rollouts), m->fused_gen, m->fused_work,
-                     m->fused_fix, m->mu, m->host.total_mass, nullptr, n_calls, true, true, kernel_events);
-  // HS_ONLINE_DEFER=1: the same online shape on hs_rollout_kernel's fused instantiation (FIX_DEFER, 4
-  // waves/SIMD, no general-path call) and its fixup + reduce per call (VERDICT r05 item 4's variant;
-  // measured, DESIGN.md section 4d)
-  const char* od = getenv("HS_ONLINE_DEFER");
-  if (od && od[0] == '1' && r.solve_mode == HS_SOLVE_AUTO && a->horizon <= HS_ONLINE_MAX_H)
-    return run_fused(d, r, ws, hs::single_model_map(m->host, a->n_rollouts), m->fused_gen, m->fused_work,
-                     m->fused_fix, m->mu, m->host.total_mass, nullptr, n_calls, false, true, kernel_events);
-  return launch_steps(d, r, ws, hs::single_model_map(m->host, a->n_rollouts), n_calls, kernel_events,
-                      m->host.total_mass, nullptr);
+  launch_ctx cx;
+  const int rc = model_ctx(m, a, n_calls, cx);
+  if (rc != HS_OK || cx.empty) return rc;
+  const hs_run_args r = routed(*a, cx.torso_mask);
+  const step_route rt = route(cx, r, run_entry::STEPS);
+  if (rt == step_route::ROLLOUT) return launch_steps(cx, r, n_calls, kernel_events);
+  return run_fused(cx, r, n_calls, rt, kernel_events);
 }
 
 int hs_run_calls(hs_model_t m, const hs_run_args* a, int32_t n_calls) {
-  int rc = check_args(m, a);
-  if (rc != HS_OK) return rc;
-  if (n_calls < 0) return fail(HS_E_ARG, "n_calls < 0");
-  if (a->n_rollouts == 0 || n_calls == 0) return HS_OK;
-  const hs_topo* d = nullptr;
-  void* ws = nullptr;
-  rc = device_state(m, a->n_rollouts + 1, a->stream, &d, &ws);
-  if (rc != HS_OK) return rc;
-  const hs_run_args r = routed(*a, m->host.torso_mask);
-  return run_fused(d, r, ws, hs::single_model_map(m->host, a->n_rollouts), m->fused_gen, m->fused_work, m->fused_fix,
-                   m->mu, m->host.total_mass, nullptr, n_calls, limb_eligible(m->host, r));
+  launch_ctx cx;
+  const int rc = model_ctx(m, a, n_calls, cx);
+  if (rc != HS_OK || cx.empty) return rc;
+  const hs_run_args r = routed(*a, cx.torso_mask);
+  return run_fused(cx, r, n_calls, route(cx, r, run_entry::CALLS));
 }
 
 int hs_run_pd(hs_model_t m, const hs_run_args* a, const hs_pd_args* pd) {
-  int rc = check_args(m, a);
-  if (rc != HS_OK) return rc;
-  if (!pd || (a->n_rollouts > 0 && (!pd->q_meas || !pd->dq_meas || !pd->tau_cmd)))
-    return fail(HS_E_ARG, "pd: q_meas, dq_meas and tau_cmd are required");
-  if (!(pd->k >= 0)) return fail(HS_E_ARG, "pd: k must be >= 0");
-  if (a->n_rollouts == 0) return HS_OK;
-  const hs_topo* d = nullptr;
-  void* ws = nullptr;
-  rc = device_state(m, a->n_rollouts + 1, a->stream, &d, &ws);
-  if (rc != HS_OK) return rc;
-  hs::launch_map mp = hs::single_model_map(m->host, a->n_rollouts);
+  launch_ctx cx;
+  const int rc = model_ctx(m, a, 1, cx, [&]() -> int {
+    if (!pd || (a->n_rollouts > 0 && (!pd->q_meas || !pd->dq_meas || !pd->tau_cmd)))
+      return fail(HS_E_ARG, "pd: q_meas, dq_meas and tau_cmd are required");
+    if (!(pd->k >= 0)) return fail(HS_E_ARG, "pd: k must be >= 0");
+    return HS_OK;
+  });
+  if (rc != HS_OK || cx.empty) return rc;
+  hs::launch_map& mp = cx.map;
   mp.pd_q = pd->q_meas;
   mp.pd_dq = pd->dq_meas;
   mp.pd_k1 = -pd->k;                 // player.cpp:394
@@ -632,96 +701,80 @@ int hs_run_pd(hs_model_t m, const hs_run_args* a, const hs_pd_args* pd) {
   mp.pd_tau = pd->tau_cmd;
   mp.pd_q0 = pd->q_target;
   mp.pd_dq0 = pd->dq_target;
-  return launch_steps(d, routed(*a, m->host.torso_mask), ws, mp, 1, nullptr, m->host.total_mass, nullptr);
+  return launch_steps(cx, routed(*a, cx.torso_mask), 1, nullptr);
 }
 
 int hs_run_forces(hs_model_t m, const hs_run_args* a, const double* tau_in) {
-  int rc = check_args(m, a);
-  if (rc != HS_OK) return rc;
-  if (a->n_rollouts > 0 && !tau_in) return fail(HS_E_ARG, "tau_in is null");
-  if (a->n_rollouts == 0) return HS_OK;
-  const hs_topo* d = nullptr;
-  void* ws = nullptr;
-  rc = device_state(m, a->n_rollouts + 1, a->stream, &d, &ws);
-  if (rc != HS_OK) return rc;
-  hs::launch_map mp = hs::single_model_map(m->host, a->n_rollouts);
-  mp.tau_in = tau_in;
-  return launch_steps(d, *a, ws, mp, 1, nullptr, m->host.total_mass, nullptr);
+  launch_ctx cx;
+  const int rc = model_ctx(m, a, 1, cx, [&]() -> int {
+    return a->n_rollouts > 0 && !tau_in ? fail(HS_E_ARG, "tau_in is null") : (int)HS_OK;
+  });
+  if (rc != HS_OK || cx.empty) return rc;
+  cx.map.tau_in = tau_in;
+  return launch_steps(cx, *a, 1, nullptr);
 }
 
 int hs_run_forces_calls(hs_model_t m, const hs_run_args* a, int32_t n_calls, const double* tau_in) {
-  int rc = check_args(m, a);
-  if (rc != HS_OK) return rc;
-  if (n_calls < 0) return fail(HS_E_ARG, "n_calls < 0");
-  if (a->n_rollouts > 0 && n_calls > 0 && !tau_in) return fail(HS_E_ARG, "tau_in is null");
-  if (a->n_rollouts == 0 || n_calls == 0) return HS_OK;
+  launch_ctx cx;
+  const int rc = model_ctx(m, a, n_calls, cx, [&]() -> int {
+    if (a->n_rollouts == 0 || n_calls == 0) return HS_OK;  // nothing to run: no further checks
+    if (!tau_in) return fail(HS_E_ARG, "tau_in is null");
+    if ((int64_t)n_calls * a->horizon > (1 << 24)) return fail(HS_E_ARG, "too many steps");
+    return HS_OK;
+  });
+  if (rc != HS_OK || cx.empty) return rc;
+  const hs::kernels& k = *cx.k;
   const int64_t S = (int64_t)n_calls * a->horizon;  // steps, one row each
-  if (S > (1 << 24)) return fail(HS_E_ARG, "too many steps");
-  const hs_topo* d = nullptr;
-  void* ws = nullptr;
-  rc = device_state(m, a->n_rollouts + 1, a->stream, &d, &ws);
-  if (rc != HS_OK) return rc;
-  hs::launch_map mp = hs::single_model_map(m->host, a->n_rollouts);
+  hs::launch_map mp = cx.map;
   mp.tau_in = tau_in;
   hs_run_args c = *a;
   c.horizon = (int32_t)S;  // output (and tau_in) rows per rollout
   c.tau = c.x = c.work_cot = nullptr;
   c.best_key = nullptr;
   // the run_fused scheme without the work reduce: hs_rollout_kernel's forces mode solves every step
-  // itself (its LDS layout runs 3 wavefronts / SIMD). The limb-lane kernel's forces mode (the model of
-  // its class, HS_SOLVE_AUTO, no q rows, fp64, the preparation pass's table) takes forces_solve's fast
-  // path and defers a step whose foot block B_f is near singular (the dense normal equations) to a
-  // fixup launch of hs_rollout_kernel's forces mode after each step launch
-  const int32_t CHUNK = std::max(1, std::min(HS_FUSED_MAX_STEPS, HS_FUSED_WAVES / std::max(1, mp.n_waves)));
+  // itself (its LDS layout runs 3 wavefronts / SIMD). The limb-lane kernel's forces mode (route(): fp64
+  // only) takes forces_solve's fast path and defers a step whose foot block B_f is near singular (the
+  // dense normal equations) to a fixup launch of hs_rollout_kernel's forces mode after each step launch
+  const int32_t CHUNK = fused_chunk(mp);
   const int32_t n_chunks = (int32_t)((S + CHUNK - 1) / CHUNK);
-  const bool f32 = a->precision == HS_PREC_F32;
   mp.fused_h = a->horizon;
-  mp.setup_only = 1;
-  mp.setup_io = hs::SETUP_STORE;
-  hs::ktab_range(a->k0, a->n_t, a->horizon, n_calls, &mp.ktab_lo, &mp.ktab_n, &mp.ttab_n);
-  const bool limb = limb_kernel_wanted() && m->host.limb_lane_ok && a->solve_mode == HS_SOLVE_AUTO && !a->q &&
-                    !f32 && mp.ktab_n > 0;
+  const bool limb = route(cx, *a, run_entry::FORCES_CALLS) == step_route::LIMB_FUSED;
   int32_t* fix_counts = nullptr;
   if (limb) {
-    const size_t counts_bytes = ((size_t)n_chunks * sizeof(int32_t) + 255) / 256 * 256;
-    const size_t bytes = counts_bytes + (size_t)CHUNK * mp.n_waves * 2 * 2 * sizeof(int32_t);
     const size_t gwb = ws_slot_bytes();
     void* fix = nullptr;
     {
-      std::lock_guard<std::mutex> lk(m->mu);
-      const hipError_t e = (hipError_t)m->fused_fix.get(a->stream, (bytes + gwb - 1) / gwb, &fix);
+      std::lock_guard<std::mutex> lk(cx.pools->mu);
+      const hipError_t e =
+          (hipError_t)cx.pools->fused_fix.get(a->stream, (fix_bytes(n_chunks, CHUNK, mp) + gwb - 1) / gwb, &fix);
       if (e != hipSuccess) return hip_fail(e, "hipMalloc(forces fixup items)");
     }
     fix_counts = (int32_t*)fix;
-    mp.fix_count = fix_counts;
-    mp.fix_n_counts = n_chunks;
-    mp.fix_items = (int32_t*)((char*)fix + counts_bytes);
+    fix_carve(fix, n_chunks, mp);
     mp.prep_unit = 8;
   }
-  int le = f32 ? hs::launch_fused_f32(d, c, ws, mp) : hs::launch_fused(d, c, ws, mp);
-  mp.setup_only = 0;
-  mp.setup_io = hs::SETUP_LOAD;
-  mp.fix_n_counts = 0;
+  int le = launch_setup(cx, c, mp);
   for (int64_t s0 = 0, ci = 0; le == 0 && s0 < S; s0 += CHUNK, ci++) {
     mp.fused_s0 = (int32_t)s0;
     mp.fused_n = (int32_t)std::min<int64_t>(CHUNK, S - s0);
     if (limb) {
       mp.fix_count = fix_counts + ci;
       mp.fix_mode = hs::FIX_DEFER;
-      le = hs::launch_limb(d, c, ws, mp);
+      le = k.launch_limb(cx.d_topo, c, cx.ws, mp);
       g_limb_launches++;
       if (le != 0) break;
       mp.fix_mode = hs::FIX_SOLVE;
       mp.fix_reduce = 0;
-      le = hs::launch_fused(d, c, ws, mp);
+      le = k.launch_fused(cx.d_topo, c, cx.ws, mp);
       mp.fix_mode = hs::FIX_NONE;
     } else {
-      le = f32 ? hs::launch_fused_f32(d, c, ws, mp) : hs::launch_fused(d, c, ws, mp);
+      le = k.launch_fused(cx.d_topo, c, cx.ws, mp);
     }
   }
   if (le != 0) return hip_fail((hipError_t)le, "kernel launch");
   return HS_OK;
 }
+
 
 int hs_mixed_create(const hs_model_t* models, int32_t n_models, const int32_t* model_index, int32_t n_rollouts,
                     hs_mixed_t* out) {
@@ -819,10 +872,7 @@ void hs_mixed_free(hs_mixed_t p) {
   if (p->d_wave_rollouts) free_on_device(p->dev, p->d_wave_rollouts);
   if (p->d_limb_model) free_on_device(p->dev, p->d_limb_model);
   if (p->d_rollout_mass) free_on_device(p->dev, p->d_rollout_mass);
-  p->ws.release();
-  p->fused_gen.release();
-  p->fused_work.release();
-  p->fused_fix.release();
+  p->release();
   delete p;
 }
 
@@ -835,72 +885,20 @@ int hs_mixed_get_dims(hs_mixed_t p, hs_model_dims* out) {
 int hs_run_mixed(hs_mixed_t p, const hs_run_args* a) { return hs_run_mixed_steps(p, a, 1, nullptr); }
 
 int hs_run_mixed_steps(hs_mixed_t p, const hs_run_args* a, int32_t n_calls, void* const* kernel_events) {
-  if (!p) return fail(HS_E_ARG, "null plan");
-  int rc = check_args(p->models[0], a);
-  if (rc != HS_OK) return rc;
-  if (a->n_rollouts != p->n_rollouts) return fail(HS_E_ARG, "n_rollouts differs from the plan's");
-  if (n_calls < 0) return fail(HS_E_ARG, "n_calls < 0");
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return hip_fail(e, "hipGetDevice");
-  if (dev != p->dev) return fail(HS_E_DEVICE, "plan was created on another device");
-  if (a->n_rollouts == 0 || n_calls == 0) return HS_OK;
-  hs::launch_map mp{};
-  mp.wave_model = p->d_wave_model;
-  mp.wave_rollouts = p->d_wave_rollouts;
-  mp.n_waves = p->n_waves;
-  mp.max_parts = p->max_dims.n_parts;
-  mp.st_tau = p->st_tau;
-  mp.st_cf = p->st_cf;
-  mp.st_q = p->st_q;
-  mp.st_x = p->st_x;
-  void* ws = nullptr;
-  {
-    std::lock_guard<std::mutex> lk(p->mu);
-    e = (hipError_t)p->ws.get(a->stream, (size_t)p->n_rollouts + 1, &ws);
-  }
-  if (e != hipSuccess) return hip_fail(e, "hipMalloc(workspace)");
-  return launch_steps(p->d_topos, routed(*a, p->torso_mask), ws, mp, n_calls, kernel_events, 0.0, p->d_rollout_mass);
+  launch_ctx cx;
+  const int rc = mixed_ctx(p, a, n_calls, cx);
+  if (rc != HS_OK || cx.empty) return rc;
+  return launch_steps(cx, routed(*a, cx.torso_mask), n_calls, kernel_events);
 }
 
 int hs_run_mixed_calls(hs_mixed_t p, const hs_run_args* a, int32_t n_calls) {
-  if (!p) return fail(HS_E_ARG, "null plan");
-  int rc = check_args(p->models[0], a);
-  if (rc != HS_OK) return rc;
-  if (a->n_rollouts != p->n_rollouts) return fail(HS_E_ARG, "n_rollouts differs from the plan's");
-  if (n_calls < 0) return fail(HS_E_ARG, "n_calls < 0");
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return hip_fail(e, "hipGetDevice");
-  if (dev != p->dev) return fail(HS_E_DEVICE, "plan was created on another device");
-  if (a->n_rollouts == 0 || n_calls == 0) return HS_OK;
-  hs::launch_map mp{};
-  mp.wave_model = p->d_wave_model;
-  mp.wave_rollouts = p->d_wave_rollouts;
-  mp.n_waves = p->n_waves;
-  mp.max_parts = p->max_dims.n_parts;
-  mp.st_tau = p->st_tau;
-  mp.st_cf = p->st_cf;
-  mp.st_q = p->st_q;
-  mp.st_x = p->st_x;
-  void* ws = nullptr;
-  {
-    std::lock_guard<std::mutex> lk(p->mu);
-    e = (hipError_t)p->ws.get(a->stream, (size_t)p->n_rollouts + 1, &ws);
-  }
-  if (e != hipSuccess) return hip_fail(e, "hipMalloc(workspace)");
-  const hs_run_args r = routed(*a, p->torso_mask);
-  bool limb = false;
-  if (p->d_limb_model) {  // every model of the plan is of the limb-lane kernel's class
-    mp.limb_model = p->d_limb_model;
-    mp.limb_rollouts = p->d_limb_rollouts;
-    mp.limb_slots = p->d_limb_rollouts + 8 * (size_t)p->limb_waves;
-    mp.limb_waves = p->limb_waves;
-    limb = limb_eligible(p->models[0]->host, r);
-  }
-  return run_fused(p->d_topos, r, ws, mp, p->fused_gen, p->fused_work, p->fused_fix, p->mu, 0.0, p->d_rollout_mass,
-                   n_calls, limb);
+  launch_ctx cx;
+  const int rc = mixed_ctx(p, a, n_calls, cx);
+  if (rc != HS_OK || cx.empty) return rc;
+  const hs_run_args r = routed(*a, cx.torso_mask);
+  return run_fused(cx, r, n_calls, route(cx, r, run_entry::CALLS));
 }
+
 
 int hs_complete_traj(hs_model_t m, const hs_gait_params* params, int32_t B, int32_t n_t, int32_t ignore_reach,
                      double* rec) {

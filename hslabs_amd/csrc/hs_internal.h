@@ -87,10 +87,6 @@ struct launch_map {
   int32_t limb_waves;
 };
 
-// Kernel launcher (hs_kernels.hip). `workspace` holds general_workspace_bytes()
-// per rollout + 1 (global-memory scratch of the conditioning fallback; the
-// extra slot serves idle half-waves). Returns a hipError_t value.
-size_t general_workspace_bytes();
 // one fused step's general-path scratch per rollout (fused_gen holds [steps in a launch][B + 1] of them)
 size_t solve_workspace_bytes();
 // the samples n_calls calls of `horizon` steps from k0 read: [lo, lo + n); the IK table holds all of
@@ -98,25 +94,30 @@ size_t solve_workspace_bytes();
 // n_ttab = min(n, its capacity)
 void ktab_range(int32_t k0, int32_t n_t, int32_t horizon, int64_t n_calls, int32_t* lo, int32_t* n_table,
                 int32_t* n_ttab);
-int launch_rollouts(const hs_topo* d_topo, const hs_run_args& a, void* workspace, const launch_map& mp);
-// single precision build of the same kernels (hs_kernels_f32.hip): outputs are float
-size_t general_workspace_bytes_f32();
-int launch_rollouts_f32(const hs_topo* d_topo, const hs_run_args& a, void* workspace, const launch_map& mp);
 launch_map single_model_map(const hs_topo& t, int32_t n_rollouts);
-// one launch of mp.fused_n fused steps (or the setup-only pass when mp.setup_only)
-int launch_fused(const hs_topo* d_topo, const hs_run_args& a, void* workspace, const launch_map& mp);
-int launch_fused_f32(const hs_topo* d_topo, const hs_run_args& a, void* workspace, const launch_map& mp);
-// the same fused step launch by the limb-lane kernel (hs_limb.h): lane = (rollout, limb), 8 rollouts per
-// wavefront; the steps it does not take are deferred to the FIX_SOLVE launch like the fused launch's
-int launch_limb(const hs_topo* d_topo, const hs_run_args& a, void* workspace, const launch_map& mp);
-int launch_limb_f32(const hs_topo* d_topo, const hs_run_args& a, void* workspace, const launch_map& mp);
-// work_cot[b] = (w, w / (total_mass * step_length)) with w = (accumulate ? work_cot[b][0] : 0) + the steps'
-// work in step order, then the best key
-// (rollout_mass: per-rollout total mass of a mixed plan, else null and total_mass)
-int launch_fused_reduce(const hs_run_args& a, double total_mass, const double* rollout_mass, const void* work_steps,
-                        int32_t n_steps);
-int launch_fused_reduce_f32(const hs_run_args& a, double total_mass, const double* rollout_mass,
-                            const void* work_steps, int32_t n_steps);
+
+// The kernel launchers of one precision's build of hs_kernels.hip (hs_kernels_f32.hip is the single
+// precision build of the same kernels: outputs are float). They return hipError_t values.
+struct kernels {
+  // `workspace` holds general_workspace_bytes() per rollout + 1 (global-memory scratch of the
+  // conditioning fallback; the extra slot serves idle half-waves)
+  size_t (*general_workspace_bytes)();
+  int (*launch_rollouts)(const hs_topo* d_topo, const hs_run_args& a, void* workspace, const launch_map& mp);
+  // one launch of mp.fused_n fused steps (or the setup-only pass when mp.setup_only)
+  int (*launch_fused)(const hs_topo* d_topo, const hs_run_args& a, void* workspace, const launch_map& mp);
+  // the same fused step launch by the limb-lane kernel (hs_limb.h): lane = (rollout, limb), 8 rollouts per
+  // wavefront; the steps it does not take are deferred to the FIX_SOLVE launch like the fused launch's
+  int (*launch_limb)(const hs_topo* d_topo, const hs_run_args& a, void* workspace, const launch_map& mp);
+  // work_cot[b] = (w, w / (total_mass * step_length)) with w = (accumulate ? work_cot[b][0] : 0) + the steps'
+  // work in step order, then the best key
+  // (rollout_mass: per-rollout total mass of a mixed plan, else null and total_mass)
+  int (*launch_fused_reduce)(const hs_run_args& a, double total_mass, const double* rollout_mass,
+                             const void* work_steps, int32_t n_steps);
+  // steps this build's limb-lane launches deferred to the fixup launch (the current device's counter)
+  int (*limb_deferred)(unsigned long long* out);
+};
+extern const kernels kernels_f64, kernels_f32;
+inline const kernels& kernels_of(int32_t precision) { return precision == HS_PREC_F32 ? kernels_f32 : kernels_f64; }
 
 // pergensetup::set_rec for n_rollouts x n_times items (hs_kernels.hip), rec [B][n_times][6 + 3 n_limbs]
 int launch_pergen_rec(const hs_topo* d_topo, const hs_gait_params* params, int32_t n_rollouts, const double* times,
@@ -161,14 +162,21 @@ struct ws_pool {
   void release();
 };
 
-struct hs_model_s {
+// The device buffers a model or a mixed plan keeps for its run calls, grown on demand under mu
+struct run_pools {
+  ws_pool ws;
+  ws_pool fused_gen, fused_work;  // hs_run_calls: general-path scratch per (step in a launch, rollout), step work
+  ws_pool fused_fix;              // hs_run_calls: fixup counters and items
+  std::mutex mu;
+  void release() {
+    for (ws_pool* p : {&ws, &fused_gen, &fused_work, &fused_fix}) p->release();
+  }
+};
+
+struct hs_model_s : run_pools {
   hs_topo host;
   hs_topo* dev[HS_MAX_DEVICES];  // per-device topology copy, created lazily
   hs_simtopo sim;                // ODE world of the model (closed-loop simulation)
   hs_simtopo* sim_dev[HS_MAX_DEVICES];
   hs_simtopo_t<float>* sim_dev_f32[HS_MAX_DEVICES];  // rounded copy for the single-precision kernel
-  ws_pool ws;
-  ws_pool fused_gen, fused_work;  // hs_run_calls: general-path scratch per (step in a launch, rollout), step work
-  ws_pool fused_fix;              // hs_run_calls: fixup counters and items
-  std::mutex mu;
 };

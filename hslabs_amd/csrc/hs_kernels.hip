@@ -3584,15 +3584,6 @@ __global__ __launch_bounds__(WAVE) void hs_pergen_rec_kernel(const hs_topo* __re
 
 }  // namespace
 
-#if HS_REAL_IS_FLOAT
-extern "C" int hs_limb_deferred_f32(unsigned long long* out) {
-#else
-extern "C" int hs_limb_deferred_f64(unsigned long long* out) {
-#endif
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_limb_deferred), sizeof(unsigned long long), 0,
-                                  hipMemcpyDeviceToHost);
-}
-
 #if defined(HS_DBG) && !HS_REAL_IS_FLOAT
 extern "C" int hs_debug_read_dbg(double* out, int n) {
   if (n > (1 << 22)) n = 1 << 22;
@@ -3617,10 +3608,15 @@ extern "C" int hs_debug_clear_stamps() {
 
 namespace hs {
 
-#if HS_REAL_IS_FLOAT
-size_t general_workspace_bytes_f32() { return sizeof(RolloutWS); }
-#else
-size_t general_workspace_bytes() { return sizeof(RolloutWS); }
+// the launchers of this build, exported as one table at the end of the file (hs::kernels)
+static size_t general_workspace_bytes() { return sizeof(RolloutWS); }
+
+static int limb_deferred(unsigned long long* out) {
+  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_limb_deferred), sizeof(unsigned long long), 0,
+                                  hipMemcpyDeviceToHost);
+}
+
+#if !HS_REAL_IS_FLOAT
 size_t solve_workspace_bytes() { return sizeof(SolveWS); }  // >= the fp32 build's
 
 void ktab_range(int32_t k0, int32_t n_t, int32_t horizon, int64_t n_calls, int32_t* lo_out, int32_t* n_out,
@@ -3665,11 +3661,7 @@ void launch_nm(const hs_topo* d_topo, const hs_run_args& a, RolloutWS* ws, const
     hipLaunchKernelGGL((hs_rollout_kernel<NM, false, FIX_NONE>), dim3(mp.n_waves), dim3(WAVE), 0, st, d_topo, a, ws, mp);
 }
 
-#if HS_REAL_IS_FLOAT
-int launch_rollouts_f32(const hs_topo* d_topo, const hs_run_args& a, void* workspace, const launch_map& mp) {
-#else
-int launch_rollouts(const hs_topo* d_topo, const hs_run_args& a, void* workspace, const launch_map& mp) {
-#endif
+static int launch_rollouts(const hs_topo* d_topo, const hs_run_args& a, void* workspace, const launch_map& mp) {
   if (a.n_rollouts <= 0 || mp.n_waves <= 0) return 0;
   hipStream_t st = (hipStream_t)a.stream;
   RolloutWS* ws = (RolloutWS*)workspace;
@@ -3693,12 +3685,7 @@ int launch_rollouts(const hs_topo* d_topo, const hs_run_args& a, void* workspace
   return 0;
 }
 
-
-#if HS_REAL_IS_FLOAT
-int launch_fused_f32(const hs_topo* d_topo, const hs_run_args& a, void* workspace, const launch_map& mp) {
-#else
-int launch_fused(const hs_topo* d_topo, const hs_run_args& a, void* workspace, const launch_map& mp) {
-#endif
+static int launch_fused(const hs_topo* d_topo, const hs_run_args& a, void* workspace, const launch_map& mp) {
   if (a.n_rollouts <= 0 || mp.n_waves <= 0) return 0;
   hipStream_t st = (hipStream_t)a.stream;
   RolloutWS* ws = (RolloutWS*)workspace;
@@ -3725,11 +3712,7 @@ int launch_fused(const hs_topo* d_topo, const hs_run_args& a, void* workspace, c
   return (int)hipGetLastError();
 }
 
-#if HS_REAL_IS_FLOAT
-int launch_limb_f32(const hs_topo* d_topo, const hs_run_args& a, void* workspace, const launch_map& mp) {
-#else
-int launch_limb(const hs_topo* d_topo, const hs_run_args& a, void* workspace, const launch_map& mp) {
-#endif
+static int launch_limb(const hs_topo* d_topo, const hs_run_args& a, void* workspace, const launch_map& mp) {
   if (a.n_rollouts <= 0 || mp.fused_n <= 0) return 0;
   hipStream_t st = (hipStream_t)a.stream;
   RolloutWS* ws = (RolloutWS*)workspace;
@@ -3753,18 +3736,24 @@ __global__ void hs_fused_reduce_kernel(hs_run_args a, real total_mass, const dou
   reduce_rollouts(a, total_mass, rollout_mass, ws, n_steps, reinterpret_cast<uint64_t*>(a.best_key), a.key_steps);
 }
 
-#if HS_REAL_IS_FLOAT
-int launch_fused_reduce_f32(const hs_run_args& a, double total_mass, const double* rollout_mass,
-                            const void* work_steps, int32_t n_steps) {
-#else
-int launch_fused_reduce(const hs_run_args& a, double total_mass, const double* rollout_mass, const void* work_steps,
-                        int32_t n_steps) {
-#endif
+static int launch_fused_reduce(const hs_run_args& a, double total_mass, const double* rollout_mass,
+                               const void* work_steps, int32_t n_steps) {
   if (a.n_rollouts <= 0 || !a.work_cot) return 0;
   // one wavefront per workgroup: B = 4096 spreads over 64 CUs instead of 16
   hipLaunchKernelGGL(hs_fused_reduce_kernel, dim3((a.n_rollouts + 63) / 64), dim3(64), 0, (hipStream_t)a.stream, a,
                      (real)total_mass, rollout_mass, (const real*)work_steps, n_steps);
   return (int)hipGetLastError();
 }
+
+// the one name that differs between the two builds of this file
+#if HS_REAL_IS_FLOAT
+#define HS_KERNELS_TABLE kernels_f32
+#else
+#define HS_KERNELS_TABLE kernels_f64
+#endif
+#ifndef __HIP_DEVICE_COMPILE__  // host only: the device pass would emit a constant-initialised const object too
+extern const kernels HS_KERNELS_TABLE = {general_workspace_bytes, launch_rollouts,     launch_fused,
+                                         launch_limb,             launch_fused_reduce, limb_deferred};
+#endif
 
 }  // namespace hs

@@ -23,43 +23,10 @@
 // the same (step, rollout) items the fused step launch defers. A mixed plan of limb-lane models runs
 // eight rollouts of one model per wavefront (launch_map::limb_model / limb_rollouts).
 
-#ifndef HS_LIMB_ROOT_BRANCHFREE
-#define HS_LIMB_ROOT_BRANCHFREE 0
-#endif
-#ifndef HS_LIMB_WORK_UNROLL
-#define HS_LIMB_WORK_UNROLL 0
-#endif
-#ifndef HS_LIMB_SAMPLE_BARRIER
-#define HS_LIMB_SAMPLE_BARRIER 1  // scheduling barriers between the stencil's samples (register pressure)
-#endif
-#ifndef HS_LIMB_LINK_BARRIER
-#define HS_LIMB_LINK_BARRIER 0  // 1: within noise at the driver command, 3 % slower at K = 200 (r06_t5)
-#endif
-#ifndef HS_LIMB_PAD
-#define HS_LIMB_PAD 1
-#endif
-#ifndef HS_LIMB_NEAR_DEFER
-#define HS_LIMB_NEAR_DEFER 0
-#endif
-#ifndef HS_LIMB_WORK_DPP
-#define HS_LIMB_WORK_DPP 0  // the joint-order work sum as a DPP chain across the limb lanes (A/B)
-#endif
-#ifndef HS_LIMB_KID_LANES
-#define HS_LIMB_KID_LANES 1  // the root's kids' range sums on lanes 0 .. nk - 1 (K = 200 +4 %, r06_t32)
-#endif
 #ifndef HS_LIMB_GROUP
 // the fused launch's block order for the limb kernel (fused_coords): groups of this many batch wavefronts
 // (8 rollouts each), each group's steps in order
 #define HS_LIMB_GROUP HS_FUSED_GROUP
-#endif
-#ifndef HS_LIMB_NC12
-#define HS_LIMB_NC12 1  // one and two contacts solved here (0: deferred, A/B)
-#endif
-#ifndef HS_LIMB_EARLY_LOADS
-#define HS_LIMB_EARLY_LOADS 0
-#endif
-#ifndef HS_LIMB_MIXED_T
-#define HS_LIMB_MIXED_T 1
 #endif
 #ifndef HS_LIMB_WAVES
 #define HS_LIMB_WAVES 2  // waves per SIMD the limb kernel is built for
@@ -125,11 +92,6 @@ template <bool CENTRE>
 __device__ __attribute__((always_inline)) inline void fk_link(const hs_topo* T, const hs_link& lk, int kk, A34& Jv,
                                                               A34& H, real s, real c, real* P, real* U, real* Jp,
                                                               real* Jz, real* fp, bool& contact) {
-#if HS_LIMB_LINK_BARRIER
-  // (a scheduling barrier per link: the machine scheduler hoists the three links' constant loads, 80 reals,
-  // to the top of the sample's block for latency, and the register allocator then spills them)
-  __builtin_amdgcn_sched_barrier(0);
-#endif
   if (kk > 0) Jv = mul(H, load34(lk.P));
   H = mul_hinge(Jv, c, s);
   {
@@ -224,9 +186,6 @@ __device__ inline BodyS body_frame(const A34& A, const real* com) {
 __device__ __attribute__((always_inline)) inline A34 limb_frame(const hs_topo* T, int L, bool straight, const bool own,
                                                                 const RolloutWS& W, int row, const real* u, real tv,
                                                                 BodyS& ob) {
-#ifdef HS_LIMB_EXP_STRAIGHT
-  straight = true;
-#endif
   if (straight) {
     if (own) ob = body_straight(W.kf.own[L][0], u, tv);
     return frame_at(load34r(W.kf.J0[L]), u, tv);
@@ -448,55 +407,7 @@ __global__ __launch_bounds__(WAVE, HS_REAL_IS_FLOAT ? HS_LIMB_WAVES_F32 : HS_LIM
   LimbLds<NM, FORCES>* lds = sh.g;
   int fstep = 0, q = (int)blockIdx.x;
   fused_coords<HS_LIMB_GROUP>((int)blockIdx.x, mp.fused_w, mp.fused_n, fstep, q);
-#if HS_LIMB_MIXED_T
   const hs_topo* __restrict__ T = mp.limb_model ? T0 + mp.limb_model[q] : T0;  // a mixed plan's wavefront model
-#else
-  const hs_topo* __restrict__ T = T0;
-#endif
-#if HS_LIMB_EARLY_LOADS
-  // the rollout's first loads (its records, sample times, torso) issued before the link records' copy and
-  // its barrier, so their latency overlaps the copy
-  RSTAMP(16);
-  STAMP(15);
-  const int lane = (int)threadIdx.x, grp = lane >> 3, l = lane & 7, gbase = lane & ~7;
-  const int b = mp.limb_rollouts ? mp.limb_rollouts[q * LGR + grp] : q * LGR + grp;
-  const bool live = b >= 0 && b < a.n_rollouts;
-  // an idle group computes a copy of a rollout of its wavefront's model and stores nothing
-  const int bb = live ? b : (mp.limb_rollouts ? mp.limb_rollouts[q * LGR] : a.n_rollouts - 1);
-  LimbLds<NM, FORCES>& S = lds[grp];
-  const int ol = grp * HS_LMAX + (l < HS_LMAX ? l : 0);  // this limb lane's column of sh.k.outer
-  const int s_glob = mp.fused_s0 + fstep, call = s_glob / mp.fused_h;
-  const int k0 = (int)(((int64_t)a.k0 + (int64_t)call * mp.fused_h) % a.n_t) + s_glob % mp.fused_h;
-  const int row0 = k0 - mp.ktab_lo;  // table row of sample i - 2 (centre i = k0 + 2)
-  const int nl = T->n_limbs, nmj = T->nmj;
-  const bool limb = l < nl, tlane = l == LG - 1;
-  const int L = limb ? l : 0;
-  const RolloutWS& W = rws[bb];
-  const hs_gait_params& gp = a.params[bb];
-  const bool straight = (real)gp.curvature == 0 && !gp.rec_transform_flag;
-  const real dt = W.st.dt;
-  const real v = W.st.v;
-  const NodeK n0 = load_nodek(T, 0);
-  const real u[3] = {n0.Jp(0, 0), n0.Jp(1, 0), n0.Jp(2, 0)};
-  real tv[5];
-#pragma unroll
-  for (int k = 0; k < 5; k += 2) tv[k] = W.t_tab[row0 + k] * v;  // gait_record's torso advance
-  // the torso COM at the centre sample (particular_sub's origin o = pos(0, 0)), on every lane
-  real o[3];
-  if (straight) {
-    for (int i = 0; i < 3; i++) o[i] = fma(tv[2], u[i], W.kf.torso[i]);
-  } else {
-    mulp(load34r(W.ktor[row0 + 2] + 6), n0.com, o);
-  }
-  const real inv = real(1) / (2 * dt);
-  {  // the link records, 8 bytes per lane and load
-    const uint64_t* src = reinterpret_cast<const uint64_t*>(&T->link[0][0]);
-    uint64_t* dst = reinterpret_cast<uint64_t*>(&sh.k.links[0][0]);
-    constexpr int NW = sizeof(sh.k.links) / sizeof(uint64_t);
-    for (int e = (int)threadIdx.x; e < NW; e += WAVE) dst[e] = src[e];
-    wave_sync();
-  }
-#else
   {  // the link records, 8 bytes per lane and load
     const uint64_t* src = reinterpret_cast<const uint64_t*>(&T->link[0][0]);
     uint64_t* dst = reinterpret_cast<uint64_t*>(&sh.k.links[0][0]);
@@ -537,7 +448,6 @@ __global__ __launch_bounds__(WAVE, HS_REAL_IS_FLOAT ? HS_LIMB_WAVES_F32 : HS_LIM
     mulp(load34r(W.ktor[row0 + 2] + 6), n0.com, o);
   }
   const real inv = real(1) / (2 * dt);
-#endif
 #ifdef HS_DBG
   const int dbg_r = live ? b * a.horizon + s_glob : -1;
 #define LDBG(slot, val, n)                                                                                       \
@@ -595,9 +505,7 @@ __global__ __launch_bounds__(WAVE, HS_REAL_IS_FLOAT ? HS_LIMB_WAVES_F32 : HS_LIM
     STAMP(1);
     // (sched_barrier: the machine scheduler would interleave the independent samples for ILP, holding
     // two samples' FK working sets at once)
-#if HS_LIMB_SAMPLE_BARRIER
     __builtin_amdgcn_sched_barrier(0);
-#endif
     {
       real P[3][3], U[3][3];
       const hs_topo* Ts = opaque_s(T);
@@ -611,9 +519,7 @@ __global__ __launch_bounds__(WAVE, HS_REAL_IS_FLOAT ? HS_LIMB_WAVES_F32 : HS_LIM
           sh.k.outer[27 + 3 * kk + j][ol] = U[kk][j];
         }
     }
-#if HS_LIMB_SAMPLE_BARRIER
     __builtin_amdgcn_sched_barrier(0);
-#endif
     STAMP(2);
     {
       const hs_topo* T = opaque_s(T_);
@@ -644,9 +550,7 @@ __global__ __launch_bounds__(WAVE, HS_REAL_IS_FLOAT ? HS_LIMB_WAVES_F32 : HS_LIM
         opaque_vals<3>(Jz[kk]);
         if (kk == 2) opaque_vals<3>(fp);
         real Pm[3], Um[3], Pp[3], Up[3];
-#if HS_LIMB_SAMPLE_BARRIER
         __builtin_amdgcn_sched_barrier(0);  // the link's outer values read here, not hoisted above its FK
-#endif
 #pragma unroll
         for (int j = 0; j < 3; j++) {
           Pm[j] = sh.k.outer[3 * kk + j][ol];
@@ -732,7 +636,6 @@ __global__ __launch_bounds__(WAVE, HS_REAL_IS_FLOAT ? HS_LIMB_WAVES_F32 : HS_LIM
       LDBG(T->limb_node[L][kk], d[0], 17);
     }
   }
-#if HS_LIMB_KID_LANES
   // the root's kids' range sums on lanes 0 .. nk - 1 of the group, in parallel (each range in preorder, as
   // the torso lane would sum it), into the kid's own slot (ranges are disjoint: no lane reads another's)
   {
@@ -765,46 +668,6 @@ __global__ __launch_bounds__(WAVE, HS_REAL_IS_FLOAT ? HS_LIMB_WAVES_F32 : HS_LIM
     V[2] -= d[0] * F[1] - d[1] * F[0];
     for (int j = 0; j < 3; j++) { S.a[j] = F[j]; S.a[3 + j] = V[j]; }
   }
-#else
-  if (tlane) {  // x_0 = (F, V - 0 x F)
-    real F[3], V[3];
-    for (int j = 0; j < 3; j++) { F[j] = S.g[0][j]; V[j] = S.g[0][3 + j]; }
-    const int nk = T->node[0].nkids;
-    for (int kk = 0; kk < HS_CMAX; kk++) {
-      if (kk >= nk) break;
-      const int c = T->node[0].kids[kk], sz = T->node[c].size;
-      real Fk[3] = {0, 0, 0}, Vk[3] = {0, 0, 0};
-#if HS_LIMB_ROOT_BRANCHFREE
-      // the range's loads issued together, without a branch per part (ranges of up to 8 parts unrolled:
-      // hexapod 7, spider 3, myant 4; a part past the range is loaded from a valid row and not added)
-#pragma unroll
-      for (int r = 0; r < 8; r++) {
-        const int rr = c + r < NM ? c + r : NM - 1;
-        real gv[6];
-        for (int j = 0; j < 6; j++) gv[j] = S.g[rr][j];
-        for (int j = 0; j < 3; j++) {
-          Fk[j] = r < sz ? Fk[j] + gv[j] : Fk[j];
-          Vk[j] = r < sz ? Vk[j] + gv[3 + j] : Vk[j];
-        }
-      }
-#else
-      // ranges of up to 8 parts unrolled (hexapod 7, spider 3, myant 4)
-#pragma unroll
-      for (int r = 0; r < 8; r++)
-        if (r < sz)
-          for (int j = 0; j < 3; j++) { Fk[j] += S.g[c + r][j]; Vk[j] += S.g[c + r][3 + j]; }
-#endif
-      for (int r = 8; r < sz; r++)
-        for (int j = 0; j < 3; j++) { Fk[j] += S.g[c + r][j]; Vk[j] += S.g[c + r][3 + j]; }
-      for (int j = 0; j < 3; j++) { F[j] += Fk[j]; V[j] += Vk[j]; }
-    }
-    const real d[3] = {0, 0, 0};
-    V[0] -= d[1] * F[2] - d[2] * F[1];
-    V[1] -= d[2] * F[0] - d[0] * F[2];
-    V[2] -= d[0] * F[1] - d[1] * F[0];
-    for (int j = 0; j < 3; j++) { S.a[j] = F[j]; S.a[3 + j] = V[j]; }
-  }
-#endif
   wave_sync();  // S.a before the Schur system reads it
 
   STAMP(5);
@@ -835,13 +698,8 @@ __global__ __launch_bounds__(WAVE, HS_REAL_IS_FLOAT ? HS_LIMB_WAVES_F32 : HS_LIM
   real d0[3] = {0, 0, 0}, Dinv[9], gc[3], Dp6[6];
   if (mine)
     for (int r = 0; r < 3; r++) d0[r] = o[r] - fp[r];  // A_c = [-I; [d0_c]x]
-  if (mine && nc >= (HS_LIMB_NC12 ? 2 : 3)) contact_block(Jp, Jz, xt, fp, Dp6, gc);
-#ifdef HS_LIMB_EXP_NOSOLVE
-  defer |= nc >= 3;
-  if (false) {
-#else
+  if (mine && nc >= 2) contact_block(Jp, Jz, xt, fp, Dp6, gc);
   if (nc >= 3) {
-#endif
     // zeroth_well_posed: the feet's scatter, in single precision, the contacts' d0 on lanes 0 .. nc - 1
     float e0 = grp_getf(float(o[0] - fp[0]), src), e1 = grp_getf(float(o[1] - fp[1]), src),
           e2 = grp_getf(float(o[2] - fp[2]), src);
@@ -961,12 +819,7 @@ __global__ __launch_bounds__(WAVE, HS_REAL_IS_FLOAT ? HS_LIMB_WAVES_F32 : HS_LIM
       opaque_vals<3>(y3);  // sv.y
     }
   }
-#if !HS_LIMB_NC12
-  defer |= nc == 1 || nc == 2;  // (A/B: one and two contacts to the fixup launch)
-  if (false) {
-#else
   if (nc == 1 || nc == 2) {
-#endif
     // fast_solve_lanes' one- and two-contact closed forms (its lane 0, from FastL): here on every lane of
     // the group, the contacts' values gathered from their limb lanes
     int s0 = 0, s1 = 0;
@@ -1074,9 +927,6 @@ __global__ __launch_bounds__(WAVE, HS_REAL_IS_FLOAT ? HS_LIMB_WAVES_F32 : HS_LIM
     }
   }
   STAMP(8);
-#if HS_LIMB_NEAR_DEFER
-  defer |= nearf;
-#endif
   if (defer) {  // the whole step to the fixup launch (hs_rollout_kernel FIX_SOLVE)
     if (l == 0 && live) {
       atomicAdd(&g_limb_deferred, 1ull);  // hs_limb_stats
@@ -1090,8 +940,6 @@ __global__ __launch_bounds__(WAVE, HS_REAL_IS_FLOAT ? HS_LIMB_WAVES_F32 : HS_LIM
   // ---- S4: motor torques, contact forces, work (step()'s outputs) ----
   const size_t orow = (size_t)b * a.horizon + s_glob;
   bool nan = false;
-  real wl[3] = {0, 0, 0};  // this limb's three work terms, its motors in link order
-  bool lm = true;          // its motors are joints 3 L, 3 L + 1, 3 L + 2 (limb-major joint order)
   if (limb) {
 #pragma unroll
     for (int kk = 0; kk < 3; kk++) {
@@ -1114,8 +962,6 @@ __global__ __launch_bounds__(WAVE, HS_REAL_IS_FLOAT ? HS_LIMB_WAVES_F32 : HS_LIM
       }
       real dw = tq * jvel[kk];
       S.wd[hh] = (dw > 0) ? dw : 0;
-      wl[kk] = (dw > 0) ? dw : 0;
-      lm &= hh == 3 * L + kk;
       nan |= tq != tq;
       if (live && a.tau) outp(a.tau)[orow * mp.st_tau + hh] = tq;
     }
@@ -1130,28 +976,13 @@ __global__ __launch_bounds__(WAVE, HS_REAL_IS_FLOAT ? HS_LIMB_WAVES_F32 : HS_LIM
   }
   // a mixed plan's rows past this model's joints and feet (hs_rollout_kernel writes them 0; a single model's
   // rows have none: the loops' code is kept off its path, ~1 % at K = 200, r06_t17)
-  if (HS_LIMB_PAD && live && mp.limb_rollouts) {
+  if (live && mp.limb_rollouts) {
     if (a.tau)
       for (int c = nmj + l; c < mp.st_tau; c += LG) outp(a.tau)[orow * mp.st_tau + c] = real(0);
     if (a.cf)
       for (int c = 3 * T->nf + l; c < mp.st_cf; c += LG) outp(a.cf)[orow * mp.st_cf + c] = real(0);
   }
   const bool any_nan = grp_any(nan, gbase), any_bad = grp_any(limb && bad, gbase);
-#if HS_LIMB_WORK_DPP
-  // the joint-order sum work_over_period takes, as a chain across the limb lanes when the joints are
-  // limb-major (lane l adds its three terms, in order, to lane l - 1's partial sum: the same additions in
-  // the same order as the loop over S.wd), else the loop
-  const bool chain = !grp_any(limb && !lm, gbase) && nmj == 3 * nl;
-  real wsum = 0;
-  if (chain) {
-    real sacc = ((real(0) + wl[0]) + wl[1]) + wl[2];
-    for (int k = 1; k < nl; k++) {
-      const real prev = dpp_r<0x111>(sacc);  // row_shr 1: lane l - 1's partial sum
-      if (l >= 1) sacc = ((prev + wl[0]) + wl[1]) + wl[2];
-    }
-    wsum = grp_get(sacc, gbase + nl - 1);
-  }
-#endif
   wave_sync();
   if (l == 0 && live) {
     uint32_t flags = 0;
@@ -1164,19 +995,7 @@ __global__ __launch_bounds__(WAVE, HS_REAL_IS_FLOAT ? HS_LIMB_WAVES_F32 : HS_LIM
     // the joints' positive work in joint order (work_over_period's loop, periodic.cpp:294-300), summed over
     // the steps in order by the reduce
     real work_dt = real(0);
-#if HS_LIMB_WORK_UNROLL
-    real wdv[HS_NMAX];
-#pragma unroll
-    for (int jj = 0; jj < HS_NMAX; jj++) wdv[jj] = S.wd[jj];  // issued together; only the nmj terms summed
-#pragma unroll
-    for (int jj = 0; jj < HS_NMAX; jj++) work_dt = jj < nmj ? work_dt + wdv[jj] : work_dt;
-#elif HS_LIMB_WORK_DPP
-    if (chain) work_dt = wsum;
-    else
-      for (int jj = 0; jj < nmj; jj++) work_dt += S.wd[jj];
-#else
     for (int jj = 0; jj < nmj; jj++) work_dt += S.wd[jj];
-#endif
     reinterpret_cast<real*>(mp.fused_work)[(size_t)s_glob * a.n_rollouts + b] = work_dt;
   }
   STAMP(9);

@@ -604,9 +604,12 @@ void hs_sim_free(hs_sim_t sim);
 
 /* The fused step launches' kernel (ABI 15). hs_run_calls takes the limb-lane kernel (lane = (rollout,
  * limb), eight rollouts per wavefront) for a model of its class (*ok = 1: every shipped
- * model), HS_SOLVE_AUTO, no x / q / dq rows, and calls whose samples fit the IK table; its outputs are
- * bitwise hs_rollout_kernel's (the steps it does not take go to the same fixup launch). HS_LIMB=0 in the
- * environment keeps hs_rollout_kernel. hs_limb_launches: the limb-lane launches this process has made. */
+ * model), HS_SOLVE_AUTO, no x / q / dq rows, and calls whose samples fit the IK table; in fp64 its outputs
+ * are bitwise hs_rollout_kernel's (the steps it does not take go to the same fixup launch). In fp32
+ * (HS_PREC_F32) they are close, not bitwise (float contraction differs by context): the tests hold torques
+ * to 1e-3 relative and flags to equality on more than 99.9 % of steps (tests/test_gpu_limb.py). HS_LIMB=0
+ * in the environment keeps hs_rollout_kernel, HS_LIMB_F32=0 keeps it for fp32 calls only.
+ * hs_limb_launches: the limb-lane launches this process has made. */
 int hs_model_limb_lane(hs_model_t model, int32_t* ok);
 int64_t hs_limb_launches(void);
 /* Diagnostics of the limb-lane kernel: its launches and the steps it deferred to the fixup launch (one,

@@ -11,6 +11,7 @@ contact forces, flags, the accumulated work and COT, and the best key (mixed pla
 build and solve_forces' forces mode are held to stated tolerances instead. Parity with the oracle then
 follows from tests/test_gpu_parity.py, which runs the default (limb-lane) path.
 """
+import contextlib
 import os
 
 import numpy as np
@@ -36,16 +37,29 @@ def hmodels(gpu):
     return {n: gpu.KinematicModel(os.path.join(MODELS, f"{n}.xml")) for n in ("hexapod", "spider", "myant")}
 
 
+@contextlib.contextmanager
+def env(**switches):
+    """the library's run-time switches (read from the environment on every call) set for the block, then
+    put back as the caller had them"""
+    old = {k: os.environ.get(k) for k in switches}
+    os.environ.update(switches)
+    try:
+        yield
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k)
+            else:
+                os.environ[k] = v
+
+
 def run(gpu, model, params, limb, K=20, Hc=1, k0=0, best=True, dtype=None, rollout_id_base=0, steps=False,
         accumulate=True):
     """K calls of Hc steps: fused (hs_run_calls, K * Hc output rows) or steps=True (hs_run_steps, a launch
     per call, each call writing rows [0, Hc); limb: its opt-in online shape, HS_LIMB_ONLINE=1)"""
     import torch
 
-    old = os.environ.get("HS_LIMB")
-    os.environ["HS_LIMB"] = "1" if limb else "0"
-    os.environ["HS_LIMB_ONLINE"] = "1" if limb and steps else "0"
-    try:
+    with env(HS_LIMB="1" if limb else "0", HS_LIMB_ONLINE="1" if limb and steps else "0"):
         b = gpu.DeviceBatch(model, params, n_t=20, k0=k0, horizon=Hc if steps else K * Hc, outputs=OUTS, dtype=dtype,
                             rollout_id_base=rollout_id_base)
         b.key_steps = K * Hc
@@ -59,12 +73,6 @@ def run(gpu, model, params, limb, K=20, Hc=1, k0=0, best=True, dtype=None, rollo
         out = {k: getattr(b, k).cpu().numpy() for k in OUTS}
         out["best_key"] = int(b.best_key.item())
         return out
-    finally:
-        os.environ.pop("HS_LIMB_ONLINE")
-        if old is None:
-            os.environ.pop("HS_LIMB")
-        else:
-            os.environ["HS_LIMB"] = old
 
 
 def same(a, b, what):
@@ -102,14 +110,37 @@ def test_limb_kernel_bitwise_equals_rollout_kernel(gpu, hmodels, name, curved, B
     assert np.isfinite(a["tau"]).all()
 
 
-def test_limb_kernel_transformed_records(gpu, hmodels):
-    """record transforms (tilted, lifted: ill-posed steps the closed form declines, deferred) mixed with
-    plain gaits in one wavefront"""
+@pytest.fixture(scope="module")
+def transformed_limb(gpu, hmodels):
+    """the transformed-records batch (hexapod, B = 512, tilted records), its limb-lane run on the default
+    path and the steps that run deferred to the fixup launch"""
     from hslabs_amd import synth
 
     rng = np.random.default_rng(17)
     p, _ = transformed(synth.gen_params(512, "hexapod", id0=900, curved=True), rng, tilt=0.05)
-    same(run(gpu, hmodels["hexapod"], p, True), run(gpu, hmodels["hexapod"], p, False), "transformed hexapod")
+    d0 = gpu.api.limb_deferred()
+    out = run(gpu, hmodels["hexapod"], p, True)
+    return p, out, gpu.api.limb_deferred() - d0
+
+
+def test_limb_kernel_transformed_records(gpu, hmodels, transformed_limb):
+    """record transforms (tilted, lifted: ill-posed steps the closed form declines, deferred) mixed with
+    plain gaits in one wavefront"""
+    p, limb, _ = transformed_limb
+    same(limb, run(gpu, hmodels["hexapod"], p, False), "transformed hexapod")
+
+
+def test_limb_kernel_transformed_records_no_fix_barrier(gpu, hmodels, transformed_limb):
+    """the same call with HS_FIX_BARRIER=0: the fixup + reduce launch without its grid barrier, each
+    workgroup fixing its own rollouts' deferred steps before it sums their work (the path of every batch
+    above 65,536 rollouts), bitwise the default path's; both runs must have deferred steps to fix"""
+    p, limb, deferred = transformed_limb
+    d0 = gpu.api.limb_deferred()
+    with env(HS_FIX_BARRIER="0"):
+        out = run(gpu, hmodels["hexapod"], p, True)
+    print(f"deferred steps: {deferred} (grid barrier), {gpu.api.limb_deferred() - d0} (HS_FIX_BARRIER=0)")
+    assert deferred > 0 and gpu.api.limb_deferred() > d0
+    same(out, limb, "transformed hexapod, HS_FIX_BARRIER=0")
 
 
 @pytest.mark.parametrize("K,Hc,k0", [(7, 3, 5), (45, 1, 13), (300, 1, 0)])
@@ -145,9 +176,7 @@ def test_limb_kernel_mixed_plan(gpu, hmodels, B, K, Hc, dtype):
     f32 = dtype == "f32"
 
     def go(limb):
-        old = os.environ.get("HS_LIMB")
-        os.environ["HS_LIMB"] = "1" if limb else "0"
-        try:
+        with env(HS_LIMB="1" if limb else "0"):
             mb = gpu.MixedBatch(ms, idx, params, n_t=20, k0=0, horizon=K * Hc, outputs=OUTS,
                                 dtype=torch.float32 if f32 else None)
             for k in ("tau", "cf"):
@@ -160,11 +189,6 @@ def test_limb_kernel_mixed_plan(gpu, hmodels, B, K, Hc, dtype):
             out = {k: getattr(mb, k).cpu().numpy() for k in OUTS}
             out["best_key"] = int(mb.best_key.item())
             return out
-        finally:
-            if old is None:
-                os.environ.pop("HS_LIMB")
-            else:
-                os.environ["HS_LIMB"] = old
 
     n0 = gpu.api.limb_launches()
     a = go(True)
@@ -202,19 +226,12 @@ def test_limb_kernel_forces_bitwise(gpu, hmodels, name, B, K, Hc, curved, straig
     tau = ctl.tau + 0.2 * torch.sin(0.7 * i + 1.3 * j)
 
     def go(limb):
-        old = os.environ.get("HS_LIMB")
-        os.environ["HS_LIMB"] = "1" if limb else "0"
-        try:
+        with env(HS_LIMB="1" if limb else "0"):
             fb = gpu.DeviceBatch(m, p, n_t=20, k0=0, horizon=K * Hc, outputs=("cf", "flags"))
             fb.cf.fill_(float("nan"))
             fb.forces_launcher(tau, K, call_horizon=Hc)()
             torch.cuda.synchronize()
             return fb.cf.cpu().numpy(), fb.flags.cpu().numpy()
-        finally:
-            if old is None:
-                os.environ.pop("HS_LIMB")
-            else:
-                os.environ["HS_LIMB"] = old
 
     n0, d0 = gpu.api.limb_launches(), gpu.api.limb_deferred()
     ca, fa = go(True)
@@ -260,11 +277,8 @@ def test_online_defer_variant_bitwise(gpu, hmodels, K, Hc, acc):
     p = synth.gen_params(777, "hexapod", id0=3, curved=True)
 
     def go(defer):
-        os.environ["HS_ONLINE_DEFER"] = "1" if defer else "0"
-        try:
+        with env(HS_ONLINE_DEFER="1" if defer else "0"):
             return run(gpu, m, p, False, K=K, Hc=Hc, steps=True, accumulate=acc)
-        finally:
-            os.environ.pop("HS_ONLINE_DEFER")
 
     same(go(True), go(False), f"online defer K={K} H={Hc}")
 
