@@ -202,6 +202,11 @@ class KinematicModel:
             pass
 
 
+def limb_tile_launches() -> int:
+    """those of limb_launches() that ran the tile mapping (hs_limb_tile_launches)"""
+    return int(capi.load().hs_limb_tile_launches())
+
+
 def limb_launches() -> int:
     """fused step launches this process made with the limb-lane kernel (hs_limb_launches)"""
     return int(capi.load().hs_limb_launches())

@@ -320,6 +320,7 @@ int launch_steps(const launch_ctx& cx, const hs_run_args& a, int32_t n_calls, vo
 }
 
 std::atomic<int64_t> g_limb_launches{0};
+std::atomic<int64_t> g_limb_tile_launches{0};  // those of them on the tile mapping
 // hs_run_steps' calls up to this horizon take the online shapes (a launch per call holds the call's
 // horizon steps; longer calls keep hs_rollout_kernel's launch per step)
 #define HS_ONLINE_MAX_H 64
@@ -327,7 +328,7 @@ std::atomic<int64_t> g_limb_launches{0};
 // A switch of the step kernels' routing, read from the environment on every call (a test switches kernels
 // within one process): one that is on by default is off at a value starting with 0, one that is off by
 // default is on at a value starting with 1. HS_LIMB (on), HS_LIMB_F32 (on), HS_LIMB_ONLINE (off),
-// HS_ONLINE_DEFER (off), HS_FIX_BARRIER (on).
+// HS_ONLINE_DEFER (off), HS_FIX_BARRIER (on), HS_LIMB_TILE (on).
 bool env_switch(const char* name, bool on_by_default) {
   const char* e = getenv(name);
   if (!e) return on_by_default;
@@ -360,6 +361,9 @@ enum class run_entry { STEPS, CALLS, FORCES_CALLS };
 //   the call fits the IK table else ONLINE_DEFER      else FUSED (also a mixed  else FUSED
 //                                                     plan without limb layout)
 //   opt-in                     HS_LIMB_ONLINE=1       -                         -
+//   tile mapping               never                  an fp64 launch of at least HS_LIMB_TILE_MIN_STEPS steps
+//   (limb_tile())                                     with a nearly full last tile, unless HS_LIMB_TILE=0
+//                                                     (both columns)
 //
 // fp32: within the single-precision build's bound of hs_rollout_kernel's float results, not bitwise
 // (float contraction differs by context: ~1e-6 relative). hs_run_steps keeps ROLLOUT past
@@ -385,6 +389,35 @@ step_route route(const launch_ctx& cx, const hs_run_args& a, run_entry entry) {
   // measured)
   if (env_switch("HS_ONLINE_DEFER", false) && a.solve_mode == HS_SOLVE_AUTO) return step_route::ONLINE_DEFER;
   return step_route::ROLLOUT;
+}
+
+// The limb-lane launch's mapping (hs_limb.h): an fp64 LIMB_FUSED launch of at least HS_LIMB_TILE_MIN_STEPS
+// steps whose last tile is nearly full runs a wavefront as one rollout x eight steps, sharing the stencil's
+// FK (the tile mapping); every other launch, and LIMB_ONLINE, keeps a wavefront as eight rollouts x one
+// step. Measured against the parent library, B = 4096, 9 interleaved rounds, the tile mapping forced at
+// every length (profiles/limb_tile_ab.txt, run 1): n = 200 +5.1 % (+5.4 % in run 2, this rule), 64 +3.8 %,
+// 40 +5.5 %, 16 +8.0 %, the mixed plan +9.2 %, forces mode +7.9 %; n = 20 (three tiles, the last half
+// empty: 24 wavefronts' lives for 20 steps) -4.3 %, n = 8 within the spread, and the fp32 build
+// (configs[2]) -4.2 %. The threshold is the smallest measured length from which every longer measured
+// one wins (16 wins but 20 loses, so 16 stays packed). The second clause is an EXTRAPOLATION, not a
+// measurement: the only launch measured with idle slots is n = 20 (4 of 24 idle, -4.3 %); taking an idle
+// slot to cost a step's share of a wavefront's life and the gain to be ~4-5 %, the tiles may idle at most
+// 1 slot in 32. Lengths with n % 8 in 1 .. 6 below 256 (the 44-step tail of a 300-step call) therefore
+// stay packed without having been measured. HS_LIMB_TILE=0 keeps every launch packed;
+// HS_LIMB_TILE_MIN=<n> in the environment (a positive decimal number; anything else is ignored) replaces
+// the whole rule by n >= <n>, fp32 included (a test runs the tile mapping at every launch length with 1).
+#ifndef HS_LIMB_TILE_MIN_STEPS
+#define HS_LIMB_TILE_MIN_STEPS 40
+#endif
+bool limb_tile(step_route rt, const hs_run_args& a, int32_t n) {
+  if (rt != step_route::LIMB_FUSED || !env_switch("HS_LIMB_TILE", true)) return false;
+  if (const char* e = getenv("HS_LIMB_TILE_MIN")) {
+    char* end = nullptr;
+    const long min_n = strtol(e, &end, 10);
+    if (end != e && *end == '\0' && min_n >= 1) return n >= min_n;
+  }
+  const int32_t idle = HS_TILE_SLOTS * limb_tile_count(n) - n;
+  return a.precision != HS_PREC_F32 && n >= HS_LIMB_TILE_MIN_STEPS && 32 * idle <= n;
 }
 
 // Steps per fused launch: the launch refills the SIMDs from its queue of wavefronts (the batch's last
@@ -488,10 +521,12 @@ int run_fused(const launch_ctx& cx, const hs_run_args& a, int32_t n_calls, step_
     mp.fix_mode = hs::FIX_DEFER;
     mp.fix_count = fix_counts + i;
     mp.fix_reduce = 0;
+    mp.limb_tile = limb_tile(rt, a, mp.fused_n);
     hipError_t e = kernel_events ? hipEventRecord((hipEvent_t)kernel_events[2 * i], st) : hipSuccess;
     if (e != hipSuccess) return hip_fail(e, "hipEventRecord");
     le = launch_step(cx.d_topo, c, cx.ws, mp);
     g_limb_launches += limb;
+    g_limb_tile_launches += mp.limb_tile;
     if (le != 0) break;
     // the same steps' declined (step, rollout) items, with the general path; together with the work
     // reduce after every online call, else after the last step launch of an HS_SOLVE_AUTO call (few
@@ -540,6 +575,7 @@ int hs_model_limb_lane(hs_model_t m, int32_t* ok) {
 }
 
 int64_t hs_limb_launches(void) { return g_limb_launches.load(); }
+int64_t hs_limb_tile_launches(void) { return g_limb_tile_launches.load(); }
 
 int hs_limb_stats(int64_t* launches, int64_t* deferred) {
   if (launches) *launches = g_limb_launches.load();
@@ -760,8 +796,10 @@ int hs_run_forces_calls(hs_model_t m, const hs_run_args* a, int32_t n_calls, con
     if (limb) {
       mp.fix_count = fix_counts + ci;
       mp.fix_mode = hs::FIX_DEFER;
+      mp.limb_tile = limb_tile(step_route::LIMB_FUSED, *a, mp.fused_n);
       le = k.launch_limb(cx.d_topo, c, cx.ws, mp);
       g_limb_launches++;
+      g_limb_tile_launches += mp.limb_tile;
       if (le != 0) break;
       mp.fix_mode = hs::FIX_SOLVE;
       mp.fix_reduce = 0;

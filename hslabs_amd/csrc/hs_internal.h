@@ -7,6 +7,7 @@
 
 #include "../../include/hslabs.h"
 #include "hs_simtopo.h"
+#include "hs_limb_tile.h"
 #include "hs_topo.h"
 
 namespace hs {
@@ -85,6 +86,10 @@ struct launch_map {
   // items) are limb_slots[...]; limb_waves wavefronts per step (null: one model, rollouts 8 w + group)
   const int32_t *limb_model, *limb_rollouts, *limb_slots;
   int32_t limb_waves;
+  // the limb-lane launch's tile mapping (hs_limb_tile.h): a wavefront runs eight steps of one rollout, the
+  // grid is limb wavefronts x 8 * limb_tile_count(fused_n) blocks, block -> (virtual step v, batch wavefront
+  // w) by fused_coords, rollout 8 w + v % 8 (limb_rollouts[...] in a mixed plan), tile v / 8
+  int32_t limb_tile;
 };
 
 // one fused step's general-path scratch per rollout (fused_gen holds [steps in a launch][B + 1] of them)

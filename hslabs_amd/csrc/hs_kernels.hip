@@ -3718,16 +3718,26 @@ static int launch_limb(const hs_topo* d_topo, const hs_run_args& a, void* worksp
   RolloutWS* ws = (RolloutWS*)workspace;
   launch_map m = mp;
   m.fused_w = mp.limb_rollouts ? mp.limb_waves : (a.n_rollouts + LGR - 1) / LGR;  // wavefronts per step: 8 rollouts each
-  const dim3 grid((unsigned)((int64_t)m.fused_w * mp.fused_n));
+  const int vsteps = mp.limb_tile ? HS_TILE_SLOTS * limb_tile_count(mp.fused_n) : mp.fused_n;
+  const dim3 grid((unsigned)((int64_t)m.fused_w * vsteps));
+  const int nm = mp.max_parts <= 18 ? 18 : (mp.max_parts <= 22 ? 22 : HS_NMAX);
+#define HS_LIMB_LAUNCH(NM_, FORCES_, TILE_) \
+  hipLaunchKernelGGL((hs_limb_kernel<NM_, FORCES_, TILE_>), grid, dim3(WAVE), 0, st, d_topo, a, ws, m)
+#define HS_LIMB_LAUNCH_NM(FORCES_, TILE_)              \
+  do {                                                 \
+    if (nm == 18) HS_LIMB_LAUNCH(18, FORCES_, TILE_);  \
+    else if (nm == 22) HS_LIMB_LAUNCH(22, FORCES_, TILE_); \
+    else HS_LIMB_LAUNCH(HS_NMAX, FORCES_, TILE_);      \
+  } while (0)
   if (mp.tau_in) {  // solve_forces (hs_run_forces_calls)
-    if (mp.max_parts <= 18) hipLaunchKernelGGL((hs_limb_kernel<18, true>), grid, dim3(WAVE), 0, st, d_topo, a, ws, m);
-    else if (mp.max_parts <= 22) hipLaunchKernelGGL((hs_limb_kernel<22, true>), grid, dim3(WAVE), 0, st, d_topo, a, ws, m);
-    else hipLaunchKernelGGL((hs_limb_kernel<HS_NMAX, true>), grid, dim3(WAVE), 0, st, d_topo, a, ws, m);
+    if (mp.limb_tile) HS_LIMB_LAUNCH_NM(true, true);
+    else HS_LIMB_LAUNCH_NM(true, false);
   } else {
-    if (mp.max_parts <= 18) hipLaunchKernelGGL((hs_limb_kernel<18, false>), grid, dim3(WAVE), 0, st, d_topo, a, ws, m);
-    else if (mp.max_parts <= 22) hipLaunchKernelGGL((hs_limb_kernel<22, false>), grid, dim3(WAVE), 0, st, d_topo, a, ws, m);
-    else hipLaunchKernelGGL((hs_limb_kernel<HS_NMAX, false>), grid, dim3(WAVE), 0, st, d_topo, a, ws, m);
+    if (mp.limb_tile) HS_LIMB_LAUNCH_NM(false, true);
+    else HS_LIMB_LAUNCH_NM(false, false);
   }
+#undef HS_LIMB_LAUNCH_NM
+#undef HS_LIMB_LAUNCH
   return (int)hipGetLastError();
 }
 

@@ -22,6 +22,11 @@
 // fixup launch (hs_rollout_kernel FIX_SOLVE), which computes it with hs_rollout_kernel's whole machinery:
 // the same (step, rollout) items the fused step launch defers. A mixed plan of limb-lane models runs
 // eight rollouts of one model per wavefront (launch_map::limb_model / limb_rollouts).
+//
+// TILE (launch_map::limb_tile, hs_limb_tile.h): the same step with the wavefront turned around -- one
+// rollout x eight steps two apart -- so that the stencil's three FK rows are shared between neighbouring
+// groups through LDS (limb_tile_kd); routed by limb_tile() in hs_capi.cpp, the same outputs bitwise
+// (tests/test_gpu_limb_tile.py).
 
 #ifndef HS_LIMB_GROUP
 // the fused launch's block order for the limb kernel (fused_coords): groups of this many batch wavefronts
@@ -386,10 +391,266 @@ __device__ __attribute__((always_inline)) inline void limb_forces(const hs_topo*
 }
 #undef FDBG
 
+// ---- the tile mapping's K and D phase ----
+// A tile-mapped wavefront is one rollout x eight steps: group g runs local step limb_tile_step(8 tile + g),
+// two steps after group g - 1's wherever the slot sequence has no break, so its stencil rows t - 2dt and
+// t + 2dt are its neighbours' centre rows. Every limb lane runs the FK of its group's centre row only and
+// stores the links' pos / ust into the outer rows of the groups that read them (sh.k.outer, the packed
+// mapping's layout: the step's lanes read their own columns as before). A row no neighbour's centre holds
+// -- the minus row of the tile's first group, the plus row of its last, both sides of a break -- is a
+// request: the first of them run in the same pass on the lanes idle in every group (l >= n_limbs), the
+// rest, eight at a time, in further passes taken only when there are any. Whether a neighbour holds a row
+// is decided from the rows themselves (row0 of the neighbour against this group's), so sharing changes
+// where a value is computed, never the value. A turning gait's chain body (its pos / ust come out of
+// limb_frame with the hip frame) is pushed from the FK's lane to the reading lane (ds_permute).
+
+// the r-th set bit of a 16-bit mask (0 when there is none)
+__device__ inline int nth_bit16(uint32_t m, int r) {
+  int sel = 0, cnt = 0;
+#pragma unroll
+  for (int i = 0; i < 16; i++) {
+    const int s = (m >> i) & 1;
+    if (s && cnt == r) sel = i;
+    cnt += s;
+  }
+  return sel;
+}
+// v sent to lane dst: a lane receives what the one lane naming it sent. A lane with nothing to send names
+// lane LG - 1 (group 0's torso lane), which is no limb's lane and reads nothing it receives
+static_assert(HS_LMAX < LG, "lane LG - 1 of a group must not be a limb lane (lane_push's idle target)");
+__device__ inline real lane_push(real v, int dst) {
+  if constexpr (sizeof(real) == 8) {
+    const double d = (double)v;
+    const int lo = __builtin_amdgcn_ds_permute(dst << 2, __double2loint(d));
+    const int hi = __builtin_amdgcn_ds_permute(dst << 2, __double2hiint(d));
+    return (real)__hiloint2double(hi, lo);
+  } else {
+    return (real)__int_as_float(__builtin_amdgcn_ds_permute(dst << 2, __float_as_int((float)v)));
+  }
+}
+
+// the K and D phase's HS_DBG values, as the packed mapping's LDBG writes them (dbg_r: b * horizon + s_glob of
+// the lane's group, -1 for an idle one)
+#ifdef HS_DBG
+#define TDBG(slot, val, n)                                                                                       \
+  do {                                                                                                           \
+    if (HS_DBG == (n) && dbg_r >= 0 && (size_t)dbg_r * 32 + (slot) < (1u << 22)) g_dbg[(size_t)dbg_r * 32 + (slot)] = (double)(val); \
+  } while (0)
+#else
+#define TDBG(slot, val, n) do {} while (0)
+#endif
+
+template <bool FORCES>
+__device__ __attribute__((always_inline)) inline void limb_tile_kd(
+    const hs_topo* T_, real (&outer)[36][LGR * HS_LMAX], hs_link (&links)[HS_LMAX][3], const RolloutWS& W, bool straight,
+    const real* u, real v, int lane, int nl, bool limb, int L, bool live, int row0, const real* tv, const real* o,
+    real inv, real dt, real (&g3)[3][6], real (&Jp)[3][3], real (&Jz)[3][3], real* fp, bool& contact, bool& own,
+    real* gown, real* jvel, real (&Pc)[3][3], real* Pown, bool& bad, bool& big, int dbg_r) {
+  (void)dbg_r;
+  const int grp = lane >> 3, l = lane & 7;
+  // which neighbour's centre row is this group's minus / plus row
+  const int rprev = __shfl(row0, (lane + WAVE - LG) & (WAVE - 1)), rnext = __shfl(row0, (lane + LG) & (WAVE - 1));
+  const uint64_t lv = __ballot(live);
+  const bool lprev = grp > 0 && ((lv >> ((lane - LG) & (WAVE - 1))) & 1);
+  const bool lnext = grp < LGR - 1 && ((lv >> ((lane + LG) & (WAVE - 1))) & 1);
+  const bool shm = live && lprev && rprev + 2 == row0;  // group g - 1's centre row is this group's minus row
+  const bool shp = live && lnext && rnext == row0 + 2;  // group g + 1's centre row is this group's plus row
+  // the requests: bit 2 g group g's minus row, bit 2 g + 1 its plus row, served in bit order
+  uint32_t M = 0;
+  {
+    const uint64_t bm = __ballot(live && !shm), bp = __ballot(live && !shp);
+#pragma unroll
+    for (int g = 0; g < LGR; g++)
+      M |= (uint32_t)((bm >> (LG * g)) & 1) << (2 * g) | (uint32_t)((bp >> (LG * g)) & 1) << (2 * g + 1);
+  }
+  const int nreq = __popc(M);
+  const int nidle = LG - nl;             // lanes of a group the step leaves idle in this phase
+  const int E0 = (LGR * nidle) / nl;     // requests the first pass takes on them
+  // the pass that serves this group's minus / plus row (a turning gait's chain body arrives with it)
+  const int rqm = __popc(M & ((1u << (2 * grp)) - 1)), rqp = __popc(M & ((1u << (2 * grp + 1)) - 1));
+  const int pm = shm || rqm < E0 ? 0 : 1 + (rqm - E0) / LGR, pp = shp || rqp < E0 ? 0 : 1 + (rqp - E0) / LGR;
+  auto col = [](int ln) { return (ln >> 3) * HS_LMAX + (ln & 7); };  // a limb lane's column of sh.k.outer
+  real P[3][3], U[3][3];  // a limb lane's links at its centre row
+  BodyS om, op, oc;       // its chain body at the three rows
+  own = limb && T_->limb_own_n[L] > 0;
+  // ---- pass 0: the centre rows on the limb lanes, the first requests on the idle lanes ----
+  {
+    int rq = 0, fL = L;
+    bool extra = false;
+    if (!limb) {
+      const int j = grp * nidle + (l - nl);
+      rq = j / nl;
+      fL = j - rq * nl;
+      extra = rq < E0 && rq < nreq;
+      if (!extra) rq = 0, fL = 0;
+    }
+    const int bit = nth_bit16(M, rq), gr = bit >> 1, side = bit & 1;
+    const int rr = __shfl(row0, gr * LG);
+    const int frow = limb ? row0 + 2 : rr + 4 * side;
+    const int dst = gr * LG + fL;
+    // the lanes whose minus / plus rows this lane's FK fills (-1: none)
+    const int dm = limb ? (shp ? lane + LG : -1) : (extra && side == 0 ? dst : -1);
+    const int dp = limb ? (shm ? lane - LG : -1) : (extra && side == 1 ? dst : -1);
+    BodyS ob;
+#pragma unroll
+    for (int j = 0; j < 3; j++) ob.P[j] = ob.U[j] = real(0);
+    if (limb || extra) {
+      const hs_topo* T = opaque_s(T_);
+      const bool fown = T->limb_own_n[fL] > 0;
+      const A34 J = limb_frame(T, fL, straight, fown, W, frow, u, W.t_tab[frow] * v, ob);
+      const real* ja = W.ktab[frow][fL];
+      real sq[3], cq[3];
+#pragma unroll
+      for (int kk = 0; kk < 3; kk++) sincos_k_small(ja[kk], &sq[kk], &cq[kk]);
+      A34 Jv = J, H;
+#pragma unroll
+      for (int kk = 0; kk < 3; kk++)
+        fk_link<true>(T, links[fL][kk], kk, Jv, H, sq[kk], cq[kk], P[kk], U[kk], Jp[kk], Jz[kk], fp, contact);
+      if (dm >= 0) {
+        const int c = col(dm);
+#pragma unroll
+        for (int kk = 0; kk < 3; kk++)
+#pragma unroll
+          for (int j = 0; j < 3; j++) {
+            outer[3 * kk + j][c] = P[kk][j];
+            outer[9 + 3 * kk + j][c] = U[kk][j];
+          }
+      }
+      if (dp >= 0) {
+        const int c = col(dp);
+#pragma unroll
+        for (int kk = 0; kk < 3; kk++)
+#pragma unroll
+          for (int j = 0; j < 3; j++) {
+            outer[18 + 3 * kk + j][c] = P[kk][j];
+            outer[27 + 3 * kk + j][c] = U[kk][j];
+          }
+      }
+    }
+    if (!limb) contact = false;
+    oc = ob;
+    if (!straight) {  // (the same on every lane: one rollout)
+#pragma unroll
+      for (int j = 0; j < 6; j++) {
+        const real val = j < 3 ? ob.P[j] : ob.U[j - 3];
+        const real vm = lane_push(val, dm >= 0 ? dm : LG - 1), vp = lane_push(val, dp >= 0 ? dp : LG - 1);  // (lane LG - 1: see lane_push)
+        if (pm == 0) (j < 3 ? om.P[j] : om.U[j - 3]) = vm;
+        if (pp == 0) (j < 3 ? op.P[j] : op.U[j - 3]) = vp;
+      }
+    }
+  }
+  STAMP(1);
+  // ---- further passes: eight requests each, request base + g on group g's limb lanes ----
+  for (int base = E0, pass = 1; base < nreq; base += LGR, pass++) {
+    const bool act = limb && base + grp < nreq;
+    const int bit = nth_bit16(M, act ? base + grp : 0), gr = bit >> 1, side = bit & 1;
+    const int frow = __shfl(row0, gr * LG) + 4 * side;
+    const int dst = act ? gr * LG + L : -1;
+    BodyS ob;
+#pragma unroll
+    for (int j = 0; j < 3; j++) ob.P[j] = ob.U[j] = real(0);
+    __builtin_amdgcn_sched_barrier(0);
+    if (act) {
+      real P2[3][3], U2[3][3];
+      bool nb = false;
+      const hs_topo* T = opaque_s(T_);
+      limb_outer(T, links[L], limb_frame(T, L, straight, own, W, frow, u, W.t_tab[frow] * v, ob), W.ktab[frow][L], P2, U2,
+                 nb);
+      const int c = col(dst), o0 = side ? 18 : 0;
+#pragma unroll
+      for (int kk = 0; kk < 3; kk++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+          outer[o0 + 3 * kk + j][c] = P2[kk][j];
+          outer[o0 + 9 + 3 * kk + j][c] = U2[kk][j];
+        }
+    }
+    if (!straight) {
+#pragma unroll
+      for (int j = 0; j < 6; j++) {
+        const real val = j < 3 ? ob.P[j] : ob.U[j - 3];
+        const real vm = lane_push(val, act && side == 0 ? dst : LG - 1), vp = lane_push(val, act && side == 1 ? dst : LG - 1);
+        if (pm == pass) (j < 3 ? om.P[j] : om.U[j - 3]) = vm;
+        if (pp == pass) (j < 3 ? op.P[j] : op.U[j - 3]) = vp;
+      }
+    }
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  STAMP(2);
+  wave_sync();  // every group's outer rows
+  if (limb) {
+    const hs_topo* T = T_;
+    if (own) {
+      if (straight) {  // kin_sample_straight's features: limb_frame's own expressions at the outer rows
+        om = body_straight(W.kf.own[L][0], u, tv[0]);
+        op = body_straight(W.kf.own[L][0], u, tv[4]);
+      }
+      part_dyn((real)T->mass[T->limb_own[L][0]], inv, om.P, oc.P, op.P, om.U, oc.U, op.U, gown);
+      part_g(oc.P, o, gown);
+      if constexpr (FORCES)
+        for (int j = 0; j < 3; j++) Pown[j] = oc.P[j];
+    }
+    const int ol = grp * HS_LMAX + l;
+#pragma unroll
+    for (int kk = 0; kk < 3; kk++) {
+      real* P0 = P[kk];
+      real* U0 = U[kk];
+      opaque_vals<3>(P0);  // the features as hs_rollout_kernel's later phases read them (LDS)
+      if constexpr (FORCES)
+        for (int j = 0; j < 3; j++) Pc[kk][j] = P0[j];
+      opaque_vals<3>(U0);
+      opaque_vals<3>(Jp[kk]);
+      opaque_vals<3>(Jz[kk]);
+      if (kk == 2) opaque_vals<3>(fp);
+      real Pm[3], Um[3], Pp[3], Up[3];
+#pragma unroll
+      for (int j = 0; j < 3; j++) {
+        Pm[j] = outer[3 * kk + j][ol];
+        Um[j] = outer[9 + 3 * kk + j][ol];
+        Pp[j] = outer[18 + 3 * kk + j][ol];
+        Up[j] = outer[27 + 3 * kk + j][ol];
+      }
+      part_dyn((real)T->mass[T->limb_node[L][kk]], inv, Pm, P0, Pp, Um, U0, Up, g3[kk]);
+      TDBG(T->limb_node[L][kk], P0[0], 1);
+      TDBG(T->limb_node[L][kk], U0[0], 5);
+      TDBG(T->limb_node[L][kk], g3[kk][0], 2);
+      TDBG(T->limb_node[L][kk], g3[kk][3], 10);
+      TDBG(T->limb_node[L][kk], g3[kk][1], 13);
+      TDBG(T->limb_node[L][kk], g3[kk][2], 14);
+      TDBG(T->limb_node[L][kk], g3[kk][4], 16);
+      if (l == 0) TDBG(31, o[0], 15);
+      if (l == 0) TDBG(30, o[1], 15);
+      TDBG(T->limb_node[L][kk], Um[0], 9);
+      TDBG(T->limb_node[L][kk], Up[0], 11);
+      TDBG(T->limb_node[L][kk], Pm[0], 12);
+      part_g(P0, o, g3[kk]);
+      TDBG(T->limb_node[L][kk], g3[kk][3], 3);
+    }
+    bad = W.kbad[row0 + 2][L] != 0;
+    // a joint value past sincos_k_small's range at any of the three rows defers the step
+#pragma unroll
+    for (int r = 0; r < 5; r += 2)
+#pragma unroll
+      for (int kk = 0; kk < 3; kk++) big |= sincos_big(W.ktab[row0 + r][L][kk]);
+    // the motors' joint rates at the centre (compute_vel_traj's wrapped difference of q at t +- dt)
+#pragma unroll
+    for (int kk = 0; kk < 3; kk++) {
+      if constexpr (FORCES) break;
+      real dd = W.ktab[row0 + 3][L][kk] - W.ktab[row0 + 1][L][kk];
+      if (dd > kPi) dd -= 2 * kPi;
+      else if (dd < -kPi) dd += 2 * kPi;
+      jvel[kk] = dd / (2 * dt);
+    }
+  }
+}
+#undef TDBG
+
 // FORCES: hs_run_forces_calls' solve_forces step (contact forces given motor torques, forces_solve's fast
 // path: a limb's blocks on its lane, the sums over the limbs in limb order by a DPP chain, the 6 x 6 on
 // every lane of the group; a B_f near singular defers the step to the forces fixup launch)
-template <int NM, bool FORCES>
+// TILE: the tile mapping (a wavefront = one rollout x eight steps, limb_tile_kd above); else a wavefront =
+// eight rollouts x one step
+template <int NM, bool FORCES, bool TILE = false>
 __global__ __launch_bounds__(WAVE, HS_REAL_IS_FLOAT ? HS_LIMB_WAVES_F32 : HS_LIMB_WAVES) void hs_limb_kernel(const hs_topo* __restrict__ T0, hs_run_args a,
                                                                       RolloutWS* __restrict__ rws, hs::launch_map mp) {
   // the outer samples' pos / ust of every lane's links (kinematics), then the groups' exchange arrays:
@@ -406,7 +667,9 @@ __global__ __launch_bounds__(WAVE, HS_REAL_IS_FLOAT ? HS_LIMB_WAVES_F32 : HS_LIM
   } sh;
   LimbLds<NM, FORCES>* lds = sh.g;
   int fstep = 0, q = (int)blockIdx.x;
-  fused_coords<HS_LIMB_GROUP>((int)blockIdx.x, mp.fused_w, mp.fused_n, fstep, q);
+  // tile mapping: the block's virtual step is (tile, rollout of the batch wavefront's eight)
+  fused_coords<HS_LIMB_GROUP>((int)blockIdx.x, mp.fused_w, TILE ? HS_TILE_SLOTS * limb_tile_count(mp.fused_n) : mp.fused_n,
+                              fstep, q);
   const hs_topo* __restrict__ T = mp.limb_model ? T0 + mp.limb_model[q] : T0;  // a mixed plan's wavefront model
   {  // the link records, 8 bytes per lane and load
     const uint64_t* src = reinterpret_cast<const uint64_t*>(&T->link[0][0]);
@@ -418,10 +681,22 @@ __global__ __launch_bounds__(WAVE, HS_REAL_IS_FLOAT ? HS_LIMB_WAVES_F32 : HS_LIM
   RSTAMP(16);
   STAMP(15);
   const int lane = (int)threadIdx.x, grp = lane >> 3, l = lane & 7, gbase = lane & ~7;
-  const int b = mp.limb_rollouts ? mp.limb_rollouts[q * LGR + grp] : q * LGR + grp;
-  const bool live = b >= 0 && b < a.n_rollouts;
+  const int rslot = q * LGR + (TILE ? fstep % LGR : grp);  // this group's rollout of the batch wavefront's eight
+  const int b = mp.limb_rollouts ? mp.limb_rollouts[rslot] : rslot;
+  bool live = b >= 0 && b < a.n_rollouts;
+  if constexpr (TILE) {
+    if (!live) return;  // the whole wavefront: one rollout
+    // group g runs slot 8 tile + g's local step. An idle group (a slot past the sequence, last tile only)
+    // takes the tile's first step for its indices, so every address it forms is valid, but it is neither a
+    // share target nor a request: its outer rows in LDS are never written, its finite differences and all
+    // that follows are computed on whatever the LDS holds (possibly NaN), and nothing of it is stored or
+    // counted (every store, atomic and fix item is gated on live)
+    const int slot0 = HS_TILE_SLOTS * (fstep / LGR), ls = limb_tile_step(slot0 + grp, mp.fused_n);
+    live = ls >= 0;
+    fstep = live ? ls : limb_tile_step(slot0, mp.fused_n);
+  }
   // an idle group computes a copy of a rollout of its wavefront's model and stores nothing
-  const int bb = live ? b : (mp.limb_rollouts ? mp.limb_rollouts[q * LGR] : a.n_rollouts - 1);
+  const int bb = live || TILE ? b : (mp.limb_rollouts ? mp.limb_rollouts[q * LGR] : a.n_rollouts - 1);
   LimbLds<NM, FORCES>& S = lds[grp];
   const int ol = grp * HS_LMAX + (l < HS_LMAX ? l : 0);  // this limb lane's column of sh.k.outer
   const int s_glob = mp.fused_s0 + fstep, call = s_glob / mp.fused_h;
@@ -484,7 +759,10 @@ __global__ __launch_bounds__(WAVE, HS_REAL_IS_FLOAT ? HS_LIMB_WAVES_F32 : HS_LIM
   real Pc[3][3], Pown[3];  // forces mode: the links' and the chain body's positions at the centre
   bool bad = false, big = false;
   const hs_topo* const T_ = T;
-  if (limb) {
+  if constexpr (TILE) {
+    limb_tile_kd<FORCES>(T_, sh.k.outer, sh.k.links, W, straight, u, v, lane, nl, limb, L, live, row0, tv, o, inv, dt, g3,
+                         Jp, Jz, fp, contact, own, gown, jvel, Pc, Pown, bad, big, live ? b * a.horizon + s_glob : -1);
+  } else if (limb) {
     const int row = row0;
     own = T->limb_own_n[L] > 0;
     // the outer samples (t - 2dt, t + 2dt): the links' pos / ust to LDS (36 reals; held in registers across
@@ -932,7 +1210,7 @@ __global__ __launch_bounds__(WAVE, HS_REAL_IS_FLOAT ? HS_LIMB_WAVES_F32 : HS_LIM
       atomicAdd(&g_limb_deferred, 1ull);  // hs_limb_stats
       const int it = atomicAdd(mp.fix_count, 1);
       mp.fix_items[2 * it] = fstep;
-      mp.fix_items[2 * it + 1] = mp.limb_slots ? mp.limb_slots[q * LGR + grp] : b;  // 2 * wavefront + half of hs_rollout_kernel's layout
+      mp.fix_items[2 * it + 1] = mp.limb_slots ? mp.limb_slots[rslot] : b;  // 2 * wavefront + half of hs_rollout_kernel's layout
     }
     return;
   }

@@ -609,9 +609,18 @@ void hs_sim_free(hs_sim_t sim);
  * (HS_PREC_F32) they are close, not bitwise (float contraction differs by context): the tests hold torques
  * to 1e-3 relative and flags to equality on more than 99.9 % of steps (tests/test_gpu_limb.py). HS_LIMB=0
  * in the environment keeps hs_rollout_kernel, HS_LIMB_F32=0 keeps it for fp32 calls only.
- * hs_limb_launches: the limb-lane launches this process has made. */
+ * hs_limb_launches: the limb-lane launches this process has made.
+ * An fp64 fused limb-lane launch of at least 40 steps whose last tile is nearly full (at most 1 idle slot
+ * in 32) runs the tile mapping instead (a wavefront = one rollout x eight steps two apart, which share the
+ * stencil's limb FK through LDS), the same outputs bitwise; shorter launches, fp32
+ * calls and hs_run_steps keep eight rollouts per wavefront. Environment: HS_LIMB_TILE=0 keeps every launch
+ * packed; HS_LIMB_TILE_MIN=<n> (a positive decimal number, else ignored) replaces the rule by "at least
+ * <n> steps" for every precision -- a test and measurement switch, slower than the rule where the rule
+ * says packed. hs_limb_tile_launches: the limb-lane launches of this process that ran the tile mapping
+ * (an additive export: HSLABS_ABI_VERSION stays 16, no existing layout or meaning changes). */
 int hs_model_limb_lane(hs_model_t model, int32_t* ok);
 int64_t hs_limb_launches(void);
+int64_t hs_limb_tile_launches(void);
 /* Diagnostics of the limb-lane kernel: its launches and the steps it deferred to the fixup launch (one,
  * two contacts, guards near their thresholds, ...) in this process; *deferred is read from the device
  * (synchronous on the current device). Either pointer may be NULL. */

@@ -1,7 +1,10 @@
 """Per-phase shader-clock breakdown of the limb-lane step kernel (hs_limb.h; diagnostic -DHS_STAMPS build
 libhslabs_stamps.so, tools/stamps.py's). Runs the bench's fused path (hexapod B = 4096, 20 calls) and prints
 mean / p50 / p90 cycles per phase over the wavefronts of one window of the launch (STEP=s: blocks from
-s * 512). Tuning aid only.   python tools/limb_stamps.py [--build]"""
+s * 512). Tuning aid only.   python tools/limb_stamps.py [--build] [--steps K] [--tile]
+--steps K: K calls instead of 20. --tile: the tile mapping at any K (HS_LIMB_TILE_MIN=1), its phases named
+as limb_tile_kd stamps them: the one FK pass (centre rows and the first requests), the further passes
+(taken at a break of the slot sequence), the exchange's barrier with the finite differences."""
 import ctypes
 import os
 import sys
@@ -18,7 +21,17 @@ PHASES = [("prelims (tv, o)", 15, 0), ("outer t-2dt FK", 0, 1), ("outer t+2dt FK
           ("contact blocks + Schur sums", 6, 7), ("6x6 + y", 7, 8), ("outputs", 8, 9), ("TOTAL", 15, 9)]
 
 
+TILE_PHASES = [("prelims (tv, o)", 15, 0), ("FK pass 0 (centres + requests)", 0, 1), ("further FK passes", 1, 2),
+               ("exchange sync + D", 2, 3)] + PHASES[4:]
+
+
 def main():
+    tile = "--tile" in sys.argv
+    K = int(sys.argv[sys.argv.index("--steps") + 1]) if "--steps" in sys.argv else 20
+    if tile:
+        os.environ["HS_LIMB_TILE_MIN"] = "1"
+    else:
+        os.environ["HS_LIMB_TILE"] = "0"
     if "--build" in sys.argv or not os.path.exists(LIB):
         B._compile(LIB, ["HS_STAMPS"])
     if "--build-only" in sys.argv:
@@ -35,18 +48,18 @@ def main():
     n = 4096
     m = H.KinematicModel(os.path.join(ROOT, "models", "hexapod.xml"))
     params = synth.gen_params(n, "hexapod")
-    b = H.DeviceBatch(m, params, n_t=20, k0=0, horizon=20, outputs=("tau", "cf", "work_cot", "flags"))
-    b.run_calls(20, best=True)
+    b = H.DeviceBatch(m, params, n_t=20, k0=0, horizon=K, outputs=("tau", "cf", "work_cot", "flags"))
+    b.run_calls(K, best=True)
     torch.cuda.synchronize()
     L.hs_debug_set_stamp_base(ctypes.c_uint(int(os.environ.get("STEP", "4")) * (n // 8)))
     L.hs_debug_clear_stamps()
-    b.run_calls(20, best=True)
+    b.run_calls(K, best=True)
     torch.cuda.synchronize()
     st = np.zeros((4096, 32), dtype=np.uint64)
     L.hs_debug_read_stamps(st.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong)), 4096)
     st = st.astype(np.int64)
     st = st[(st[:, 9] != 0) & (st[:, 15] != 0)]
-    for name, a, c in PHASES:
+    for name, a, c in (TILE_PHASES if tile else PHASES):
         d = st[:, c] - st[:, a]
         print(f"{name:28s} mean {d.mean():9.0f}  p50 {np.median(d):9.0f}  p90 {np.percentile(d, 90):9.0f}  (n={len(d)})")
     t0 = st[:, 16].min()
