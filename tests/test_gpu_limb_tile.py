@@ -232,8 +232,8 @@ def test_forces_mode(gpu, hmodels):
 
 def test_fp32(gpu, hmodels):
     """the single-precision build, configs[2]'s call shape: finite wherever the packed run is, the same
-    flags, torques within the fp32 build's bound of the packed run (tests/test_gpu_limb.py's: 1e-3
-    relative)"""
+    flags, torques and contact forces within the fp32 build's bound of the packed run
+    (tests/test_gpu_limb.py's: 1e-3 relative)"""
     import torch
     from hslabs_amd import synth
 
@@ -249,6 +249,10 @@ def test_fp32(gpu, hmodels):
           f"flags differ on {int((t['flags'] != pk['flags']).sum())} steps")
     assert np.array_equal(t["flags"], pk["flags"])
     assert err[ok].max() < 1e-3
+    okc = np.isfinite(t["cf"]) & np.isfinite(pk["cf"])
+    errc = np.abs(t["cf"].astype(np.float64) - pk["cf"]) / np.maximum(1.0, np.abs(pk["cf"].astype(np.float64)))
+    print(f"fp32 tile against packed: max relative contact force difference {errc[okc].max():.3e}")
+    assert errc[okc].max() < 1e-3
 
 
 def test_routing_rule(gpu, hmodels):

@@ -364,7 +364,9 @@ def test_full_rank_steps_match_oracle(gpu, hmodels, oracle_mod, omodels):
 
 def test_fp32_configs2_matches_fp64_oracle(gpu, hmodels, oracle_mod, omodels):
     """BASELINE configs[2] (spider, 16384 rollouts x horizon 32, fp32) against the fp64 oracle
-    directly (round 1 compared fp32 only with the fp64 kernel). A foot whose height is within
+    directly (round 1 compared fp32 only with the fp64 kernel). The kernel exercised is
+    hs_rollout_kernel<float>, through b.run (hs_run -> hs_run_steps); bench.py --fp32 goes through
+    hs_run_calls, whose fp32 limb-lane kernel tests/test_gpu_limb_oracle.py holds to the oracle. A foot whose height is within
     rounding of the contact threshold (rcap + 1e-4) may switch contact sets between precisions; such
     steps are counted, and must be rare."""
     import torch
