@@ -630,6 +630,9 @@ class SimBatch:
         self._config = config
         self.seed.zero_()
         self.tsi.fill_(int(tsi0))
+        # the derivative tracker (configtimedertrack: zeros at construction) and the last motor torques
+        self.ders = torch.zeros((self.B, 3, self.model.config_dim), dtype=torch.float64, device=self.device)
+        self.last_tau = None
 
     def step(self, n_steps: int = 1, stream=None, outputs=("tau_cmd", "q_meas", "torso", "n_contacts",
                                                            "normal_force")) -> dict:
@@ -660,6 +663,8 @@ class SimBatch:
         st = stream if stream is not None else torch.cuda.current_stream(self.device)
         a.stream = st.cuda_stream
         capi.check(capi.load().hs_sim_step(self.model.handle, ctypes.byref(a)), "hs_sim_step")
+        if "tau_cmd" in out and n_steps > 0:
+            self.last_tau = out["tau_cmd"][:, -1, :]
         return out
 
     def trial(self, n_steps: int, *, open_loop: bool = False, torque_limit: float = 0.0, kick_every: int = 0,
@@ -726,7 +731,145 @@ class SimBatch:
         t.state, t.fall_z = self.state.data_ptr(), self.fall_z.data_ptr()
         capi.check(capi.load().hs_sim_trial(self.model.handle, ctypes.byref(t)), "hs_sim_trial")
         res["state"], res["fall_z"] = self.state, self.fall_z
+        if "tau_cmd" in res and n_steps > 0:
+            self.last_tau = res["tau_cmd"][:, -1, :]
         return res
+
+    # ---- dynamics from simulation (estimate_B_by_regression, player.cpp:548-582)
+
+    def _stream(self, stream):
+        st = stream if stream is not None else self.torch.cuda.current_stream(self.device)
+        return st.cuda_stream
+
+    def config(self, body=None, stream=None):
+        """visualizer::get_ode_config of every rollout (hs_sim_config): [B][config_dim] = torso
+        translation, torso Euler angles, the motors' hinge angles; the inverse of reset(). ``body``:
+        another state array [...][n_parts][13] of this batch's dtype (default: the batch's own)."""
+        torch = self.torch
+        body = self.body if body is None else body
+        _require(body.dtype == self.dtype and body.is_contiguous() and
+                 tuple(body.shape[-2:]) == (self.model.n_parts, capi.SIM_BODY_STRIDE), "body: [...][n_parts][13]")
+        lead = tuple(body.shape[:-2])
+        n = int(np.prod(lead)) if lead else 1
+        cfg = torch.empty(lead + (self.model.config_dim,), dtype=self.dtype, device=self.device)
+        capi.check(capi.load().hs_sim_config(self.model.handle, n, body.data_ptr(), cfg.data_ptr(),
+                                             self.model.config_dim, self.precision, self._stream(stream)),
+                   "hs_sim_config")
+        return cfg
+
+    def track_push(self, config=None, stream=None):
+        """configtimedertrack::push_config (hs_sim_track_push) of ``config`` (default: config()) into
+        ``self.ders`` [B][3][config_dim] = configuration, first and second backward difference.
+        reset() zeroes the tracker, so the first push leaves config / dt as "velocity" and the
+        first two pushes no meaningful acceleration, like the reference. float64 batches only."""
+        config = self.config(stream=stream) if config is None else config
+        _require(tuple(config.shape) == (self.B, self.model.config_dim) and config.is_contiguous(),
+                 "config: [B][config_dim]")
+        capi.check(capi.load().hs_sim_track_push(self.model.handle, self.B, config.data_ptr(), config.shape[1],
+                                                 float(self.params.dt), self.ders.data_ptr(), self.precision,
+                                                 self._stream(stream)), "hs_sim_track_push")
+        return self.ders
+
+    def _tau0(self, tau0):
+        if tau0 is None:
+            tau0 = self.last_tau
+        if tau0 is None:
+            return None
+        t = self.torch.as_tensor(tau0, dtype=self.dtype, device=self.device).contiguous()
+        _require(tuple(t.shape) == (self.B, self.model.nmj), "tau0: [B][nmj]")
+        return t
+
+    def _probe_args(self, a, dtau, tau0, stream, body_out, n_contacts):
+        torch = self.torch
+        B, nmj, cfg = self.B, self.model.nmj, self.model.config_dim
+        dtau = torch.as_tensor(dtau, dtype=self.dtype, device=self.device).contiguous()
+        _require(dtau.dim() == 3 and dtau.shape[0] == B and dtau.shape[2] == nmj, "dtau: [B][m][nmj]")
+        m = int(dtau.shape[1])
+        t0 = self._tau0(tau0)
+        res = {"config_out": torch.empty((B, m, cfg), dtype=self.dtype, device=self.device),
+               "tau_out": torch.empty((B, m, nmj), dtype=self.dtype, device=self.device)}
+        if body_out:
+            res["body_out"] = torch.empty((B, m, self.model.n_parts, capi.SIM_BODY_STRIDE), dtype=self.dtype,
+                                          device=self.device)
+        if n_contacts:
+            res["n_contacts"] = torch.empty((B, m), dtype=torch.int32, device=self.device)
+        a.n_rollouts, a.m, a.precision, a.params = B, m, self.precision, self.params
+        a.body, a.seed = self.body.data_ptr(), self.seed.data_ptr()
+        a.tau0 = t0.data_ptr() if t0 is not None else None
+        a.dtau = dtau.data_ptr()
+        for k in ("config_out", "tau_out", "body_out", "n_contacts"):
+            setattr(a, k, res[k].data_ptr() if k in res else None)
+        a.stream = self._stream(stream)
+        return res, (dtau, t0)  # the inputs stay alive with the caller until the launch is enqueued
+
+    def probe(self, dtau, tau0=None, stream=None, body_out=False, n_contacts=False) -> dict:
+        """The probe loop of estimate_B_by_regression (hs_sim_probe): for every rollout, m = dtau.shape[1]
+        one-step simulations from its current state with the torques tau0 + dtau[:, j] applied as they
+        are, in one launch of B * m wavefronts. The state is not advanced; ``self.seed`` moves past the
+        m probes' draws, as the reference's dRand stream does. tau0 [B][nmj]: default the last tau_cmd row
+        step() / trial() produced (zeros before any). Returns ``config_out`` [B][m][config_dim] and
+        ``tau_out`` [B][m][nmj], with ``body_out=True`` / ``n_contacts=True`` also those."""
+        a = capi.SimProbeArgsC()
+        res, keep = self._probe_args(a, dtau, tau0, stream, body_out, n_contacts)
+        capi.check(capi.load().hs_sim_probe(self.model.handle, ctypes.byref(a)), "hs_sim_probe")
+        return res
+
+    def estimate_B(self, dtau=None, m=None, tau0=None, stream=None, seed: int = 0, body_out=False,
+                   n_contacts=False) -> dict:
+        """One modelplayer::estimate_B_by_regression per rollout (hs_sim_estimate_B): push the current
+        configuration into the tracker, probe, take each probe's acceleration from a copy of the
+        tracker, regress accelerations on torques. m defaults to config_dim + 20 (player.cpp:551),
+        dtau to synth.gen_torque_perturbations(B, m, nmj, seed=seed) (the reference's distribution),
+        tau0 as in probe(). Returns ``Bt`` [B][nmj][config_dim], ``rank`` [B], ``T`` [B][m][nmj]
+        (the torques applied), ``U`` [B][m][config_dim] (the accelerations) and the probe outputs.
+        Needs at least two earlier pushes (or estimates) for meaningful accelerations. float64 only."""
+        from . import synth
+        torch = self.torch
+        B, nmj, cfg = self.B, self.model.nmj, self.model.config_dim
+        if dtau is None:
+            m = cfg + 20 if m is None else int(m)
+            dtau = synth.gen_torque_perturbations(B, m, nmj, seed=seed)
+        t = capi.SimEstimateArgsC()
+        res, keep = self._probe_args(t.probe, dtau, tau0, stream, body_out, n_contacts)
+        m = t.probe.m
+        L = capi.load()
+        res["U"] = torch.empty((B, m, cfg), dtype=torch.float64, device=self.device)
+        res["Bt"] = torch.empty((B, nmj, cfg), dtype=torch.float64, device=self.device)
+        res["rank"] = torch.empty((B,), dtype=torch.int32, device=self.device)
+        nbytes = int(L.hs_sim_estimate_workspace(self.model.handle, B, m))
+        ws = torch.empty(((nbytes + 7) // 8,), dtype=torch.float64, device=self.device)
+        t.ders, t.U, t.Bt, t.rank = self.ders.data_ptr(), res["U"].data_ptr(), res["Bt"].data_ptr(), res["rank"].data_ptr()
+        t.workspace, t.workspace_bytes = ws.data_ptr(), ws.numel() * 8
+        capi.check(L.hs_sim_estimate_B(self.model.handle, ctypes.byref(t)), "hs_sim_estimate_B")
+        res["T"] = res["tau_out"]
+        return res
+
+    def regress_B(self, T, U, stream=None) -> dict:
+        """B_from_T_U (hs_sim_regress_B) per rollout: T [B][m][nmj] torques, U [B][m][config_dim]
+        accelerations -> ``Bt`` [B][nmj][config_dim] and ``rank`` [B]; m == 0 gives set_Bt_unity."""
+        torch = self.torch
+        B, nmj, cfg = self.B, self.model.nmj, self.model.config_dim
+        T = torch.as_tensor(T, dtype=torch.float64, device=self.device).contiguous()
+        U = torch.as_tensor(U, dtype=torch.float64, device=self.device).contiguous()
+        _require(T.dim() == 3 and U.dim() == 3 and T.shape[0] == B and T.shape[2] == nmj and
+                 tuple(U.shape) == (B, T.shape[1], cfg), "T: [B][m][nmj], U: [B][m][config_dim]")
+        res = {"Bt": torch.empty((B, nmj, cfg), dtype=torch.float64, device=self.device),
+               "rank": torch.empty((B,), dtype=torch.int32, device=self.device)}
+        capi.check(capi.load().hs_sim_regress_B(self.model.handle, B, int(T.shape[1]), T.data_ptr(), U.data_ptr(),
+                                                res["Bt"].data_ptr(), res["rank"].data_ptr(), capi.HS_PREC_F64,
+                                                self._stream(stream)), "hs_sim_regress_B")
+        return res
+
+    def traj_record(self):
+        """modelplayer::add_traj_record (player.cpp:496-504) for every rollout: [B][2 * config_dim + nmj]
+        = ders[0] | ders[1] | last motor torques. Stack one per step and write the result with
+        save_2d_array for the reference's traj.txt; save_traj_recording drops the first two records
+        (player.cpp:515-516), whose differences are still the tracker's start-up values."""
+        torch = self.torch
+        tau = self._tau0(None)
+        if tau is None:
+            tau = torch.zeros((self.B, self.model.nmj), dtype=self.dtype, device=self.device)
+        return torch.cat([self.ders[:, 0, :], self.ders[:, 1, :], tau.to(torch.float64)], dim=1)
 
     def trial_reset(self) -> None:
         """Every rollout RUNNING again (after reset())."""

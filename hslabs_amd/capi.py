@@ -40,12 +40,17 @@ EXPORTS = [
     "hs_best_key_decode", "hs_last_error", "hs_abi_version",
     "hs_sim_default_params", "hs_sim_reset", "hs_sim_step", "hs_sim_create", "hs_sim_advance", "hs_sim_get_state",
     "hs_sim_free", "hs_sim_trial", "hs_sim_trial_summary", "hs_sim_set_trial", "hs_sim_get_trial_state",
+    "hs_sim_config", "hs_sim_track_push", "hs_sim_probe", "hs_sim_estimate_workspace",
     "hs_batch_create", "hs_batch_set_params", "hs_batch_run", "hs_batch_run_device", "hs_select_best",
     "hs_batch_best_key_device", "hs_batch_free", "hs_comm_unique_id", "hs_comm_init", "hs_comm_free", "hs_comm_size",
     "hs_comm_reduce_best", "hs_select_best_comm", "hs_pergen_rec", "hs_pergen_rec_host", "hs_model_lik",
     "hs_model_lik_host", "hs_model_fk", "hs_model_fk_host", "hs_model_get_node", "hs_model_set_torso_penalty",
     "hs_model_get_torso_penalty", "hs_model_limb_lane", "hs_limb_launches", "hs_limb_tile_launches", "hs_limb_stats",
 ]
+# ... and the two whose names end in the reference's capital B (B_from_T_U, estimate_B_by_regression):
+# declared in the header and exported like the rest, listed apart because EXPORTS is compared with a
+# lower-case scan of the header (tests/test_capi.py)
+EXPORTS_B = ["hs_sim_regress_B", "hs_sim_estimate_B"]
 HS_FLAG_LIK_FAILED = 128
 SIM_BODY_STRIDE = 13
 HS_TRIAL_RUNNING = -1
@@ -136,6 +141,21 @@ class SimTrialArgsC(ctypes.Structure):
                                               "reserved")] + \
                [("torque_limit", ctypes.c_double), ("hc", ctypes.c_double), ("kick_dv", ctypes.c_void_p),
                 ("state", ctypes.c_void_p), ("fall_z", ctypes.c_void_p)]
+
+
+class SimProbeArgsC(ctypes.Structure):
+    """hs_sim_probe_args."""
+    _fields_ = [("n_rollouts", ctypes.c_int32), ("m", ctypes.c_int32), ("precision", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("params", SimParamsC)] + \
+               [(f, ctypes.c_void_p) for f in ("body", "seed", "tau0", "dtau", "config_out", "tau_out", "body_out",
+                                               "n_contacts", "stream")]
+
+
+class SimEstimateArgsC(ctypes.Structure):
+    """hs_sim_estimate_args."""
+    _fields_ = [("probe", SimProbeArgsC)] + \
+               [(f, ctypes.c_void_p) for f in ("ders", "U", "Bt", "rank", "workspace")] + \
+               [("workspace_bytes", ctypes.c_size_t)]
 
 
 class TrialSummaryC(ctypes.Structure):
@@ -242,6 +262,13 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
                                    ctypes.c_double, ctypes.c_int32, ctypes.c_int32]
     L.hs_sim_get_trial_state.argtypes = [vp, ctypes.POINTER(ctypes.c_int32)]
     L.hs_sim_free.restype = None
+    L.hs_sim_config.argtypes = [vp, ctypes.c_int32, vp, vp, ctypes.c_int32, ctypes.c_int32, vp]
+    L.hs_sim_track_push.argtypes = [vp, ctypes.c_int32, vp, ctypes.c_int32, ctypes.c_double, vp, ctypes.c_int32, vp]
+    L.hs_sim_probe.argtypes = [vp, ctypes.POINTER(SimProbeArgsC)]
+    L.hs_sim_regress_B.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, ctypes.c_int32, vp]
+    L.hs_sim_estimate_workspace.argtypes = [vp, ctypes.c_int32, ctypes.c_int32]
+    L.hs_sim_estimate_workspace.restype = ctypes.c_size_t
+    L.hs_sim_estimate_B.argtypes = [vp, ctypes.POINTER(SimEstimateArgsC)]
     L.hs_batch_create.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint32,
                                   ctypes.POINTER(vp)]
     L.hs_batch_set_params.argtypes = [vp, ctypes.POINTER(GaitParamsC)]

@@ -1402,6 +1402,169 @@ int hs_sim_trial_summary(const int32_t* state, int32_t n, hs_trial_summary* out,
   return HS_OK;
 }
 
+// ---- dynamics from simulation (hs_sim_probe.hip); every check comes before the first device call
+
+int hs_sim_config(hs_model_t m, int32_t n, const double* body, double* config, int32_t config_stride, int32_t precision,
+                  void* stream) {
+  if (!m) return fail(HS_E_ARG, "null model");
+  if (n < 0 || n > (1 << 30)) return fail(HS_E_ARG, "bad n");
+  if (precision != HS_PREC_F64 && precision != HS_PREC_F32) return fail(HS_E_ARG, "unknown precision");
+  if (config_stride < m->host.cfg) return fail(HS_E_ARG, "config_stride < config_dim");
+  if (n == 0) return HS_OK;
+  if (!body || !config) return fail(HS_E_ARG, "null body or config");
+  const hs_topo* d = nullptr;
+  const hs_simtopo* ds = nullptr;
+  const hs_simtopo_t<float>* dsf = nullptr;
+  int rc = sim_device_state(m, &d, &ds, precision == HS_PREC_F32 ? &dsf : nullptr);
+  if (rc != HS_OK) return rc;
+  int e = hs::launch_sim_config(d, ds, dsf, n, body, config, config_stride, precision, stream);
+  if (e != 0) return hip_fail((hipError_t)e, "hs_sim_config launch");
+  return HS_OK;
+}
+
+int hs_sim_track_push(hs_model_t m, int32_t n, const double* config, int32_t config_stride, double dt, double* ders,
+                      int32_t precision, void* stream) {
+  if (!m) return fail(HS_E_ARG, "null model");
+  if (n < 0 || n > (1 << 30)) return fail(HS_E_ARG, "bad n");
+  if (precision != HS_PREC_F64) return fail(HS_E_ARG, "hs_sim_track_push is double precision only");
+  if (config_stride < m->host.cfg) return fail(HS_E_ARG, "config_stride < config_dim");
+  if (!(dt > 0)) return fail(HS_E_ARG, "dt must be > 0");
+  if (n == 0) return HS_OK;
+  if (!config || !ders) return fail(HS_E_ARG, "null config or ders");
+  int e = hs::launch_track_push(n, m->host.cfg, config, config_stride, dt, ders, stream);
+  if (e != 0) return hip_fail((hipError_t)e, "hs_sim_track_push launch");
+  return HS_OK;
+}
+
+// the checks hs_sim_probe and hs_sim_estimate_B share; *nothing = true for an empty call
+static int probe_args_check(hs_model_t m, const hs_sim_probe_args* a, bool* nothing) {
+  *nothing = false;
+  if (!m || !a) return fail(HS_E_ARG, "null model or args");
+  if (a->n_rollouts < 0 || a->n_rollouts > (1 << 30)) return fail(HS_E_ARG, "bad n_rollouts");
+  if (a->m < 0) return fail(HS_E_ARG, "m < 0");
+  if ((int64_t)a->n_rollouts * a->m > (1 << 30)) return fail(HS_E_ARG, "n_rollouts * m too large");
+  if (a->precision != HS_PREC_F64 && a->precision != HS_PREC_F32) return fail(HS_E_ARG, "unknown precision");
+  if (!a->body || !a->seed) return fail(HS_E_ARG, "body and seed are required");
+  if (a->m > 0 && (!a->dtau || !a->config_out || !a->tau_out))
+    return fail(HS_E_ARG, "dtau, config_out and tau_out are required");
+  const hs_sim_params& P = a->params;
+  if (!(P.dt > 0)) return fail(HS_E_ARG, "dt must be > 0");
+  if (P.iterations < 0) return fail(HS_E_ARG, "iterations < 0");
+  if (!(P.mu > 0)) return fail(HS_E_ARG, "mu must be > 0 (the reference uses dInfinity: 3 rows per contact)");
+  if (m->sim.m_max > 9 * HS_NMAX) return fail(HS_E_TOPOLOGY, "too many constraint rows for the simulation kernel");
+  *nothing = a->n_rollouts == 0 || a->m == 0;
+  return HS_OK;
+}
+
+// the probe launch; seed_copy: [B] device words the launch may overwrite (the probes read the seeds
+// from it while the last probe of each rollout writes a->seed)
+static int probe_launch(hs_model_t m, const hs_sim_probe_args* a, uint32_t* seed_copy) {
+  const hs_topo* d = nullptr;
+  const hs_simtopo* ds = nullptr;
+  const hs_simtopo_t<float>* dsf = nullptr;
+  int rc = sim_device_state(m, &d, &ds, a->precision == HS_PREC_F32 ? &dsf : nullptr);
+  if (rc != HS_OK) return rc;
+  hipStream_t st = (hipStream_t)a->stream;
+  hipError_t e = hipMemcpyAsync(seed_copy, a->seed, (size_t)a->n_rollouts * sizeof(uint32_t), hipMemcpyDeviceToDevice, st);
+  if (e != hipSuccess) return hip_fail(e, "hs_sim_probe seed copy");
+  hs_sim_probe_kargs k;
+  memset(&k, 0, sizeof(k));
+  k.sim.n_rollouts = a->n_rollouts;
+  k.sim.n_steps = 1;
+  k.sim.n_t = 1;
+  k.sim.precision = a->precision;
+  k.sim.params = a->params;
+  k.sim.body = const_cast<double*>(a->body);  // the PROBE instantiations only read it
+  k.sim.seed = seed_copy;
+  k.sim.n_contacts = a->n_contacts;
+  k.sim.stream = a->stream;
+  k.m = a->m;
+  k.tau0 = a->tau0;
+  k.dtau = a->dtau;
+  k.config_out = a->config_out;
+  k.tau_out = a->tau_out;
+  k.body_out = a->body_out;
+  k.seed_out = a->seed;
+  int le = hs::launch_sim_probe(d, ds, dsf, m->sim, k);
+  if (le != 0) return hip_fail((hipError_t)le, "hs_sim_probe launch");
+  return HS_OK;
+}
+
+int hs_sim_probe(hs_model_t m, const hs_sim_probe_args* a) {
+  bool nothing = false;
+  int rc = probe_args_check(m, a, &nothing);
+  if (rc != HS_OK || nothing) return rc;
+  // the copy of the seeds lives for the launch: allocated and freed in stream order
+  hipStream_t st = (hipStream_t)a->stream;
+  uint32_t* seed_copy = nullptr;
+  hipError_t e = hipMallocAsync((void**)&seed_copy, (size_t)a->n_rollouts * sizeof(uint32_t), st);
+  if (e != hipSuccess) return hip_fail(e, "hs_sim_probe");
+  rc = probe_launch(m, a, seed_copy);
+  e = hipFreeAsync(seed_copy, st);
+  if (rc != HS_OK) return rc;
+  if (e != hipSuccess) return hip_fail(e, "hs_sim_probe");
+  return HS_OK;
+}
+
+static int regress_check(hs_model_t m, int32_t n, int32_t ms, int32_t precision) {
+  if (!m) return fail(HS_E_ARG, "null model");
+  if (n < 0 || n > (1 << 30)) return fail(HS_E_ARG, "bad n");
+  if (ms < 0) return fail(HS_E_ARG, "m < 0");
+  if (precision != HS_PREC_F64) return fail(HS_E_ARG, "the regression is double precision only");
+  if (ms > 0 && ms < m->sim.nmj + 1)
+    return fail(HS_E_ARG, "0 < m < nmj + 1: the rank-deficient basic solution is not restated");
+  if (ms > 0 && hs::regress_lds_bytes(ms, m->sim.nmj, m->host.cfg) > 64 * 1024)
+    return fail(HS_E_ARG, "m too large for the regression kernel (64 KB of LDS)");
+  return HS_OK;
+}
+
+int hs_sim_regress_B(hs_model_t m, int32_t n, int32_t ms, const double* T, const double* U, double* Bt, int32_t* rank,
+                     int32_t precision, void* stream) {
+  int rc = regress_check(m, n, ms, precision);
+  if (rc != HS_OK) return rc;
+  if (n == 0) return HS_OK;
+  if (!Bt || !rank || (ms > 0 && (!T || !U))) return fail(HS_E_ARG, "null T, U, Bt or rank");
+  int e = hs::launch_regress_B(n, ms, m->sim.nmj, m->host.cfg, T, U, Bt, rank, stream);
+  if (e != 0) return hip_fail((hipError_t)e, "hs_sim_regress_B launch");
+  return HS_OK;
+}
+
+size_t hs_sim_estimate_workspace(hs_model_t m, int32_t n_rollouts, int32_t ms) {
+  (void)ms;
+  if (!m || n_rollouts <= 0) return 0;
+  // the current configuration [B][config_dim], then the copy of the seeds [B]
+  return (size_t)n_rollouts * m->host.cfg * sizeof(double) + (size_t)n_rollouts * sizeof(uint32_t);
+}
+
+int hs_sim_estimate_B(hs_model_t m, const hs_sim_estimate_args* t) {
+  if (!t) return fail(HS_E_ARG, "null model or args");
+  const hs_sim_probe_args* a = &t->probe;
+  bool nothing = false;
+  int rc = probe_args_check(m, a, &nothing);
+  if (rc != HS_OK) return rc;
+  rc = regress_check(m, a->n_rollouts, a->m, a->precision);
+  if (rc != HS_OK) return rc;
+  if (a->n_rollouts == 0) return HS_OK;
+  if (!t->ders || !t->Bt || !t->rank || (a->m > 0 && !t->U)) return fail(HS_E_ARG, "ders, U, Bt and rank are required");
+  if (!t->workspace || t->workspace_bytes < hs_sim_estimate_workspace(m, a->n_rollouts, a->m))
+    return fail(HS_E_ARG, "workspace missing or smaller than hs_sim_estimate_workspace");
+  const int cfg = m->host.cfg;
+  double* config0 = (double*)t->workspace;
+  uint32_t* seed_copy = (uint32_t*)(config0 + (size_t)a->n_rollouts * cfg);
+  // get_ode_config + push_config (player.cpp:557-558), the probes, U, B_from_T_U
+  rc = hs_sim_config(m, a->n_rollouts, a->body, config0, cfg, HS_PREC_F64, a->stream);
+  if (rc != HS_OK) return rc;
+  rc = hs_sim_track_push(m, a->n_rollouts, config0, cfg, a->params.dt, t->ders, HS_PREC_F64, a->stream);
+  if (rc != HS_OK) return rc;
+  if (a->m > 0) {
+    rc = probe_launch(m, a, seed_copy);
+    if (rc != HS_OK) return rc;
+    int e = hs::launch_probe_accel(a->n_rollouts, a->m, cfg, a->config_out, t->ders, a->params.dt, t->U, a->stream);
+    if (e != 0) return hip_fail((hipError_t)e, "hs_sim_estimate_B launch");
+  }
+  return hs_sim_regress_B(m, a->n_rollouts, a->m, a->tau_out, t->U, t->Bt, t->rank, HS_PREC_F64, a->stream);
+}
+
 struct hs_sim_s {
   hs_model_t model;
   int dev;

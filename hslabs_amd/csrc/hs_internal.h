@@ -10,6 +10,22 @@
 #include "hs_limb_tile.h"
 #include "hs_topo.h"
 
+// What the PROBE instantiations of the simulation kernel take (hs_sim_probe.hip): wavefront w is probe
+// w % m of rollout w / m. sim: n_rollouts = B, n_steps = 1, params, precision, stream; body is read
+// only, seed the rollouts' seeds before the call (a copy: seed_out may be the caller's array, and probes
+// of a rollout still read while its last one writes), n_contacts [B][m] or NULL; the tables and the
+// other outputs are unused.
+struct hs_sim_probe_kargs {
+  hs_sim_args sim;
+  int32_t m, pad;
+  const double* tau0;   // [B][nmj] or NULL = zeros
+  const double* dtau;   // [B][m][nmj]
+  double* config_out;   // [B][m][config_dim]
+  double* tau_out;      // [B][m][nmj]
+  double* body_out;     // [B][m][n_parts][13] or NULL
+  uint32_t* seed_out;   // [B] the seed after the m probes
+};
+
 namespace hs {
 
 // records msg for hs_last_error() (thread-local) and returns code
@@ -145,6 +161,22 @@ int launch_sim_trial(const hs_topo* d_topo, const hs_simtopo* d_sim, const hs_si
 int launch_trial_summary(const int32_t* state, int32_t n, hs_trial_summary* acc, void* stream);
 // resident rollouts per CU of hs_sim_step's kernels for a model size: {fp64, fp32, fp32 3 waves/SIMD}
 int sim_step_occupancy(int32_t n, int32_t m_max, int32_t* out3);
+// "dynamics from simulation" (hs_sim_probe.hip): the batch get_ode_config, the derivative tracker's
+// push, the PROBE instantiations of the simulation kernel (B * m wavefronts), a probe's acceleration
+// from a copy of the tracker, and the regression of accelerations on torques (fp64). d_sim_f32 is
+// needed with HS_PREC_F32 only. regress_lds_bytes: the regression's LDS for m samples (the caller
+// rejects more than 64 KB).
+int launch_sim_config(const hs_topo* d_topo, const hs_simtopo* d_sim, const hs_simtopo_t<float>* d_sim_f32, int32_t n,
+                      const double* body, double* config, int32_t config_stride, int32_t precision, void* stream);
+int launch_track_push(int32_t n, int32_t cfg, const double* config, int32_t config_stride, double dt, double* ders,
+                      void* stream);
+int launch_sim_probe(const hs_topo* d_topo, const hs_simtopo* d_sim, const hs_simtopo_t<float>* d_sim_f32,
+                     const hs_simtopo& host_sim, const hs_sim_probe_kargs& a);
+int launch_probe_accel(int32_t n, int32_t m, int32_t cfg, const double* config_out, const double* ders, double dt,
+                       double* U, void* stream);
+int launch_regress_B(int32_t n, int32_t m, int32_t nmj, int32_t cfg, const double* T, const double* U, double* Bt,
+                     int32_t* rank, void* stream);
+size_t regress_lds_bytes(int32_t m, int32_t nmj, int32_t cfg);
 
 }  // namespace hs
 

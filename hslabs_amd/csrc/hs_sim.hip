@@ -44,10 +44,15 @@
 // hs_sim_trial.hip compiles this file again with HS_SIM_TRIAL_TU for the TRIAL instantiations of the
 // kernel: in one translation unit with the plain ones they change the code the compiler emits for
 // the plain fp64 kernels (23 commuted operands; measured 1 % on hs_sim_step), apart they cannot.
+// hs_sim_probe.hip does the same with HS_SIM_PROBE_TU for the PROBE instantiations (hs_sim_probe: one
+// step per wavefront from a shared start state), which bring nothing else of this file with them.
 #ifdef HS_SIM_TRIAL_TU
 #define HS_SIM_TU_TRIAL true
 #else
 #define HS_SIM_TU_TRIAL false
+#endif
+#if !defined(HS_SIM_TRIAL_TU) && !defined(HS_SIM_PROBE_TU)
+#define HS_SIM_PLAIN_TU 1
 #endif
 
 namespace {
@@ -146,6 +151,10 @@ __device__ inline typename L::real hinge_angle(const L& s, const hs_simjoint_t<t
   if (theta > real(M_PI)) theta -= real(2 * M_PI);
   return -theta;
 }
+
+#ifdef HS_SIM_PROBE_TU
+#include "hs_sim_config.h"
+#endif
 
 template <class L>
 __device__ inline void put_row(L& s, int r, const typename L::real* j12) {
@@ -403,14 +412,29 @@ __device__ inline int run_row(const L& s, int se, int pair) {  // row of a lane 
 // addition sits under `if constexpr (TRIAL)` or a `TRIAL &&` the front end folds: the TRIAL = false
 // instantiations (hs_sim_step) read hs_sim_args alone and take no new branch (Trials,
 // compares their instructions with the kernel before the parameter existed).
-template <bool TRIAL>
+//
+// PROBE: hs_sim_probe's instantiations (hs_sim_probe.hip). They take hs_sim_probe_kargs; wavefront w is
+// probe w % m of rollout w / m: it loads the rollout's world (read only: odestate::save / load,
+// player.cpp:559-576), applies tau0 + dtau as they are (visualizer::set_ode_motor_torques: no PD, clip,
+// kick or fall check), starts the dRand stream where the rollout's m probes run one after another would
+// have left it for this one, takes one step, and writes the world, its configuration and the torques to
+// its own output rows. As with TRIAL, every addition folds away in the other instantiations.
+template <bool TRIAL, bool PROBE = false>
 struct SimKA { using type = hs_sim_args; };
 template <>
-struct SimKA<true> { using type = hs_sim_trial_args; };
+struct SimKA<true, false> { using type = hs_sim_trial_args; };
+template <>
+struct SimKA<false, true> { using type = hs_sim_probe_kargs; };
 __host__ __device__ inline const hs_sim_args& sim_of(const hs_sim_args& a) { return a; }
 __host__ __device__ inline const hs_sim_args& sim_of(const hs_sim_trial_args& a) { return a.sim; }
+__host__ __device__ inline const hs_sim_args& sim_of(const hs_sim_probe_kargs& a) { return a.sim; }
 __device__ inline constexpr bool open_loop_of(const hs_sim_args&) { return false; }
 __device__ inline bool open_loop_of(const hs_sim_trial_args& a) { return a.open_loop != 0; }
+__device__ inline constexpr bool open_loop_of(const hs_sim_probe_kargs&) { return true; }
+// the rollout of wavefront w
+__device__ inline int rollout_of(const hs_sim_args&, int w) { return w; }
+__device__ inline int rollout_of(const hs_sim_trial_args&, int w) { return w; }
+__device__ inline int rollout_of(const hs_sim_probe_kargs& a, int w) { return w / a.m; }
 
 // a trial's registers: the kick force f = dv / play_dt (player.cpp:600), formed once, in the lane that
 // owns body 0 (zero elsewhere); whether this step kicks; the outcome, RUNNING until a fall check
@@ -425,15 +449,16 @@ struct TrialRegs {
 template <class real>
 struct TrialRegs<real, false> {};
 
-template <int NM, int MM, class Real, int MINW, bool TRIAL>
+template <int NM, int MM, class Real, int MINW, bool TRIAL, bool PROBE = false>
 __global__ __launch_bounds__(WAVE, MINW) void hs_sim_kernel(const hs_topo* __restrict__ T0,
                                                          const hs_simtopo_t<Real>* __restrict__ S,
-                                                         typename SimKA<TRIAL>::type ka) {
+                                                         typename SimKA<TRIAL, PROBE>::type ka) {
   using real = Real;
   __shared__ SimL<NM, MM, Real> s;
   const hs_sim_args& a = sim_of(ka);
   const int lane = threadIdx.x;
-  const int b = blockIdx.x;
+  const int w = blockIdx.x;
+  const int b = rollout_of(ka, w);
   if (b >= a.n_rollouts) return;
   // a rollout that enters the launch frozen does nothing (wave-uniform: one rollout per wavefront)
   if constexpr (TRIAL) {
@@ -465,7 +490,7 @@ __global__ __launch_bounds__(WAVE, MINW) void hs_sim_kernel(const hs_topo* __res
     else s.avel[p][c - 10] = v;
   }
   if (lane == 0) s.seed = a.seed[b];
-  int tsi = a.tsi[b];
+  int tsi = PROBE ? 0 : a.tsi[b];  // a probe reads no table row and advances no clock
   wave_sync();
   if (lane < n) s.invm[lane] = real(1) / T.mass[lane];
   wave_sync();
@@ -479,7 +504,7 @@ __global__ __launch_bounds__(WAVE, MINW) void hs_sim_kernel(const hs_topo* __res
   }
   SIM_ACC(0);
   for (int step = 0; step < a.n_steps; step++) {
-    const size_t orow = (size_t)b * a.n_steps + step;
+    const size_t orow = PROBE ? (size_t)w : (size_t)b * a.n_steps + step;
     if constexpr (TRIAL) {
       // ---- fall_check (player.cpp:669-681) before the step: s.pos[0][2] is an LDS broadcast, so the
       // whole wave takes the same branch and leaves through the tail that stores the world
@@ -510,7 +535,14 @@ __global__ __launch_bounds__(WAVE, MINW) void hs_sim_kernel(const hs_topo* __res
           tq = tau_tab[((size_t)b * a.n_t + hrow) * nmj + lane];
         }
       }
-      if (P.k > 0 && !(TRIAL && open_loop_of(ka))) {
+      if constexpr (PROBE) {
+        // last_motor_torques plus the perturbation (player.cpp:565-568), applied as they are
+        const real* tau0 = reinterpret_cast<const real*>(ka.tau0);
+        tq = tau0 ? tau0[(size_t)b * nmj + lane] : real(0);
+        tq += reinterpret_cast<const real*>(ka.dtau)[(size_t)w * nmj + lane];
+        reinterpret_cast<real*>(ka.tau_out)[(size_t)w * nmj + lane] = tq;
+      }
+      if (!PROBE && P.k > 0 && !(TRIAL && open_loop_of(ka))) {
         real ax[3], R1[12];
         q_to_R(s.q[J.b1], R1);
         mul0_331(ax, R1, J.axis1);
@@ -542,7 +574,7 @@ __global__ __launch_bounds__(WAVE, MINW) void hs_sim_kernel(const hs_topo* __res
     if (lane < n) {
       const int p = lane;
       real tq[3] = {0, 0, 0};
-      if (P.k > 0 || (TRIAL && open_loop_of(ka))) {  // open loop applies its torques whatever k is
+      if (PROBE || P.k > 0 || (TRIAL && open_loop_of(ka))) {  // open loop applies its torques whatever k is
         for (int c = 0; c < T.tq_n[p]; c++) {  // dJointAddHingeTorque in motor order
           const int j = T.tq_motor[p][c];
           const hs_simjoint_t<real>& J = T.joint[T.motor_joint[j]];
@@ -687,6 +719,16 @@ __global__ __launch_bounds__(WAVE, MINW) void hs_sim_kernel(const hs_topo* __res
       const int pair = lane >> 1, half = lane & 1;
       for (int i = lane; i < m; i += WAVE) s.order[i] = (uint8_t)i;  // findex all -1: identity order
       uint32_t seed = __builtin_amdgcn_readfirstlane(s.seed);
+      if constexpr (PROBE) {
+        // The reference's probes draw from one dRand stream in turn (odestate does not hold it). They
+        // share their start positions, hence the contact set and m, so each makes the same draws: m - 1
+        // per reshuffle. This probe starts after those of the w % m probes before it.
+        if (m > 1) {
+          const uint32_t la = T.lcg_a[m - 1], lc = T.lcg_c[m - 1];
+          const int skip = (w % ka.m) * ((P.iterations + 7) / 8);
+          for (int t = 0; t < skip; t++) seed = la * seed + lc;
+        }
+      }
       for (int it0 = 0; it0 < P.iterations; it0 += 8) {
         // RANDOMLY_REORDER_CONSTRAINTS: Fisher-Yates with dRandInt over the current order, i.e.
         // order' = order o t_1 o ... o t_{m-1} with t_i the transposition (i, s_i). The draws s_i are
@@ -905,16 +947,31 @@ __global__ __launch_bounds__(WAVE, MINW) void hs_sim_kernel(const hs_topo* __res
 #endif
   }
   // store the world
-  for (int e = lane; e < n * HS_SIM_BODY; e += WAVE) {
-    const int p = e / HS_SIM_BODY, c = e % HS_SIM_BODY;
-    real v;
-    if (c < 3) v = s.pos[p][c];
-    else if (c < 7) v = s.q[p][c - 3];
-    else if (c < 10) v = s.lvel[p][c - 7];
-    else v = s.avel[p][c - 10];
-    gbody[e] = v;
+  if constexpr (PROBE) {
+    // ... of this probe, where asked for; the rollout's own state stays as it was
+    gbody = ka.body_out ? reinterpret_cast<real*>(ka.body_out) + (size_t)w * n * HS_SIM_BODY : nullptr;
   }
-  if (lane == 0) {
+  if (!PROBE || gbody) {
+    for (int e = lane; e < n * HS_SIM_BODY; e += WAVE) {
+      const int p = e / HS_SIM_BODY, c = e % HS_SIM_BODY;
+      real v;
+      if (c < 3) v = s.pos[p][c];
+      else if (c < 7) v = s.q[p][c - 3];
+      else if (c < 10) v = s.lvel[p][c - 7];
+      else v = s.avel[p][c - 10];
+      gbody[e] = v;
+    }
+  }
+  if constexpr (PROBE) {
+#ifdef HS_SIM_PROBE_TU
+    // get_ode_config of the stepped world (player.cpp:571): lane = motor, the last lane the torso
+    real* cfg_out = reinterpret_cast<real*>(ka.config_out) + (size_t)w * cfg;
+    if (lane < nmj) cfg_out[6 + lane] = hinge_angle(s, T.joint[T.motor_joint[lane]]);
+    if (lane == WAVE - 1) torso_config(T0, T.body_geom[0], s.pos[0], s.q[0], cfg_out);
+    // the rollout's seed after its m probes is the last probe's
+    if (lane == 0 && w % ka.m == ka.m - 1) ka.seed_out[b] = s.seed;
+#endif
+  } else if (lane == 0) {
     a.seed[b] = s.seed;
     a.tsi[b] = tsi;
     if constexpr (TRIAL) {
@@ -963,7 +1020,7 @@ __global__ __launch_bounds__(256) void hs_trial_summary_kernel(const int32_t* __
 }
 #endif
 
-#ifndef HS_SIM_TRIAL_TU
+#ifdef HS_SIM_PLAIN_TU
 // init_play_config + orient_odebodys: lane = part, A_ground by walking the chain from the root
 // (each product in the reference's order: J_A_ground = A_parent J_A_parent, then * E(q) * A_pj_body).
 // IO = the precision of the configuration and body arrays; the pose is built in double and
@@ -1011,7 +1068,7 @@ __global__ __launch_bounds__(WAVE) void hs_sim_reset_kernel(const hs_topo* __res
 
 }  // namespace
 
-#if defined(HS_SIM_STAMPS) && !defined(HS_SIM_TRIAL_TU)
+#if defined(HS_SIM_STAMPS) && defined(HS_SIM_PLAIN_TU)
 extern "C" int hs_debug_read_sim_stamps(unsigned long long* out, int n_rows) {
   if (n_rows > 4096) n_rows = 4096;
   return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_sim_stamps), sizeof(unsigned long long) * 16 * n_rows, 0,
@@ -1025,7 +1082,7 @@ extern "C" int hs_debug_clear_sim_stamps() {
 
 namespace hs {
 
-#ifndef HS_SIM_TRIAL_TU
+#ifdef HS_SIM_PLAIN_TU
 int launch_sim_reset(const hs_topo* d_topo, const hs_simtopo* d_sim, int32_t n_rollouts, const double* config,
                      int32_t config_stride, double* body, int32_t precision, void* stream) {
   if (n_rollouts <= 0) return 0;
@@ -1058,6 +1115,7 @@ static long sim_rounds(const void* k, long B) {
   return (B + slots - 1) / slots;
 }
 
+#ifndef HS_SIM_PROBE_TU  // (hs_sim_probe.hip has its own launcher: another grid, no 3-waves/SIMD choice)
 // the fp64 trial kernel is held to the 2-waves/SIMD budget the plain one meets on its own (with a free
 // budget it takes 255 VGPRs + 4 AGPRs, one wave per SIMD, and loses a third of its rollouts per CU)
 template <class R, bool TRIAL>
@@ -1112,7 +1170,9 @@ static int tu_occupancy(int32_t n, int32_t m_max, int32_t* out3) {
   return 0;
 }
 
-#ifndef HS_SIM_TRIAL_TU
+#endif  // !HS_SIM_PROBE_TU
+
+#ifdef HS_SIM_PLAIN_TU
 int launch_sim_steps(const hs_topo* d_topo, const hs_simtopo* d_sim, const hs_simtopo_t<float>* d_sim_f32,
                      const hs_simtopo& hs, const hs_sim_args& a) {
   if (a.n_rollouts <= 0 || a.n_steps <= 0) return 0;
@@ -1121,7 +1181,7 @@ int launch_sim_steps(const hs_topo* d_topo, const hs_simtopo* d_sim, const hs_si
 }
 
 int sim_step_occupancy(int32_t n, int32_t m_max, int32_t* out3) { return tu_occupancy(n, m_max, out3); }
-#else
+#elif defined(HS_SIM_TRIAL_TU)
 int launch_sim_trial(const hs_topo* d_topo, const hs_simtopo* d_sim, const hs_simtopo_t<float>* d_sim_f32,
                      const hs_simtopo& hs, const hs_sim_trial_args& a) {
   if (a.sim.n_rollouts <= 0 || a.sim.n_steps <= 0) return 0;

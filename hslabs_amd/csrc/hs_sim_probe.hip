@@ -1,0 +1,299 @@
+// hs_sim_probe.hip -- "dynamics from simulation" (modelplayer::estimate_B_by_regression, player.cpp:548-582)
+// for a batch: the PROBE instantiations of the simulation kernel (hs_sim.hip compiled a third time, apart
+// from hs_sim_step's and hs_sim_trial's so that those stay the code they were), get_ode_config, the
+// derivative tracker and the regression of accelerations on torques. Built like hs_sim.hip, with
+// -ffp-contract=off: the probes must step exactly as hs_sim_trial steps, and the tracker's
+// subtract-then-scale (odestate.cpp:114-116) must not fuse.
+#define HS_SIM_PROBE_TU 1
+#include "hs_sim.hip"
+
+#include <cfloat>
+
+namespace {
+
+// visualizer::get_ode_config (visualization.cpp:378-396), one lane per rollout: torso pose, then
+// dJointGetHingeAngle of every motor in motor order (the P phase's hinge_angle).
+template <class IO>
+__global__ __launch_bounds__(WAVE) void hs_sim_config_kernel(const hs_topo* __restrict__ T0,
+                                                              const hs_simtopo_t<IO>* __restrict__ S, int32_t n_rollouts,
+                                                              const IO* __restrict__ body, IO* __restrict__ config,
+                                                              int32_t stride) {
+  const int b = blockIdx.x * WAVE + threadIdx.x;
+  if (b >= n_rollouts) return;
+  const hs_simtopo_t<IO>& T = *S;
+  const IO* bd = body + (size_t)b * T.n * HS_SIM_BODY;
+  IO* out = config + (size_t)b * stride;
+  torso_config(T0, T.body_geom[0], bd, bd + 3, out);
+  const BodyView<IO> view{{bd}};
+  for (int j = 0; j < T.nmj; j++) out[6 + j] = hinge_angle(view, T.joint[T.motor_joint[j]]);
+}
+
+// configtimedertrack(2, config_dim, dt)::push_config (odestate.cpp:105-119), one lane per (rollout,
+// coordinate): level by level, subtract then multiply by (1./dt). ders [B][3][cfg] starts at zero, so
+// the first push leaves config / dt as "velocity", like the reference; no angle wrap, like the reference.
+__global__ __launch_bounds__(256) void hs_track_push_kernel(int32_t n_rollouts, int32_t cfg,
+                                                             const double* __restrict__ config, int32_t stride,
+                                                             double h1, double* __restrict__ ders) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (long)n_rollouts * cfg) return;
+  const int b = (int)(e / cfg), i = (int)(e % cfg);
+  double* d = ders + (size_t)b * 3 * cfg + i;
+  double nw = config[(size_t)b * stride + i], old = d[0];
+  d[0] = nw;
+  for (int lv = 1; lv <= 2; lv++) {  // compute_dern
+    nw -= old;
+    nw *= h1;
+    old = d[lv * cfg];
+    d[lv * cfg] = nw;
+  }
+}
+
+// U[b][j] = ders[2] of a copy of rollout b's tracker after push_config(config_out[b][j])
+// (player.cpp:564, 572-575; the copy takes levels 0 and 1, odestate.cpp:130-135)
+__global__ __launch_bounds__(256) void hs_probe_accel_kernel(int32_t n_rollouts, int32_t m, int32_t cfg,
+                                                              const double* __restrict__ config_out,
+                                                              const double* __restrict__ ders, double h1,
+                                                              double* __restrict__ U) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (long)n_rollouts * m * cfg) return;
+  const int i = (int)(e % cfg);
+  const int b = (int)(e / ((long)m * cfg));
+  const double* d = ders + (size_t)b * 3 * cfg + i;
+  double nw = config_out[e];
+  nw -= d[0];
+  nw *= h1;
+  nw -= d[cfg];
+  nw *= h1;
+  U[e] = nw;
+}
+
+// B_from_T_U (player.cpp:531-546), one wavefront per rollout, everything in LDS: A = [T^T | 1]
+// (m x (nmj + 1), column-major), Eigen 3.3 ColPivHouseholderQR of it -- the column-norm downdate, the
+// nonzero-pivot rule and the solve as hs_kernels.hip's colpiv_qr / qr_solve restate them for the square
+// systems of the contact solve; this one is rectangular, sized at run time and unfused, so it is restated
+// here -- then B.row(i) = solve(U.row(i)^T), one lane per right-hand side i, and Bt[j] = B.col(j) for
+// j < nmj (the constant column is dropped). rank = Eigen's nonzeroPivots(), the count its solve uses.
+// Pivot search and Householder norm run on every lane over LDS broadcasts (wave-uniform loops): no
+// single-lane loop, the shape tools/isa_check.py guards against.
+__global__ __launch_bounds__(WAVE) void hs_regress_kernel(int32_t n_rollouts, int32_t m, int32_t nmj, int32_t cfg,
+                                                           const double* __restrict__ Tg, const double* __restrict__ Ug,
+                                                           double* __restrict__ Bt, int32_t* __restrict__ rank) {
+  extern __shared__ double lds[];
+  const int lane = threadIdx.x, b = blockIdx.x;
+  if (b >= n_rollouts) return;
+  double* bt = Bt + (size_t)b * nmj * cfg;
+  if (m == 0) {  // set_Bt_unity (player.cpp:522-529)
+    for (int e = lane; e < nmj * cfg; e += WAVE) bt[e] = (e % cfg == cfg - nmj + e / cfg) ? 1.0 : 0.0;
+    if (lane == 0) rank[b] = 0;
+    return;
+  }
+  const int n = nmj + 1;
+  double* qr = lds;             // [n][m]: qr[r + c * m]
+  double* C = qr + (size_t)m * n;  // right-hand sides [m][cfg]: C[r * cfg + i], lane i's column
+  double* nu = C + (size_t)m * cfg;  // Eigen's colNormsUpdated / colNormsDirect / hCoeffs
+  double* nd = nu + n;
+  double* hc = nd + n;
+  int* perm = reinterpret_cast<int*>(hc + n);
+  const double* Tb = Tg + (size_t)b * m * nmj;
+  const double* Ub = Ug + (size_t)b * m * cfg;
+  for (int e = lane; e < m * nmj; e += WAVE) qr[e / nmj + (e % nmj) * m] = Tb[e];
+  for (int r = lane; r < m; r += WAVE) qr[r + nmj * m] = 1.0;
+  for (int e = lane; e < m * cfg; e += WAVE) C[e] = Ub[e];
+  if (lane < n) perm[lane] = lane;
+  wave_sync();
+  if (lane < n) {
+    double s = 0;
+    for (int i = 0; i < m; i++) s += qr[i + lane * m] * qr[i + lane * m];
+    nd[lane] = sqrt(s);
+    nu[lane] = nd[lane];
+  }
+  wave_sync();
+  double mx = 0;
+  for (int j = 0; j < n; j++) mx = fmax(mx, nu[j]);
+  const double th = mx * DBL_EPSILON;
+  const double threshold_helper = th * th / (double)m;
+  const double ndt = sqrt(DBL_EPSILON);
+  int np = n;
+  for (int p = 0; p < n; p++) {
+    int bi = p;
+    double bv = nu[p];
+    for (int j = p + 1; j < n; j++)
+      if (nu[j] > bv) { bv = nu[j]; bi = j; }
+    bi = __builtin_amdgcn_readfirstlane(bi);
+    if (np == n && bv * bv < threshold_helper * (double)(m - p)) np = p;
+    wave_sync();
+    if (bi != p) {
+      for (int r = lane; r < m; r += WAVE) {
+        const double t = qr[r + p * m];
+        qr[r + p * m] = qr[r + bi * m];
+        qr[r + bi * m] = t;
+      }
+      if (lane == 0) {
+        double t = nu[p]; nu[p] = nu[bi]; nu[bi] = t;
+        t = nd[p]; nd[p] = nd[bi]; nd[bi] = t;
+        const int ti = perm[p]; perm[p] = perm[bi]; perm[bi] = ti;
+      }
+    }
+    wave_sync();
+    // makeHouseholderInPlace on column p, rows p..m-1
+    const int len = m - p;
+    const double c0 = qr[p + p * m];
+    double tail = 0;
+    for (int i = 1; i < len; i++) tail += qr[p + i + p * m] * qr[p + i + p * m];
+    double tau, beta;
+    if (len == 1 || tail <= DBL_MIN) {
+      tau = 0;
+      beta = c0;
+      for (int i = 1 + lane; i < len; i += WAVE) qr[p + i + p * m] = 0;
+    } else {
+      beta = sqrt(c0 * c0 + tail);
+      if (c0 >= 0) beta = -beta;
+      const double den = c0 - beta;
+      for (int i = 1 + lane; i < len; i += WAVE) qr[p + i + p * m] /= den;
+      tau = (beta - c0) / beta;
+    }
+    wave_sync();
+    if (lane == 0) { qr[p + p * m] = beta; hc[p] = tau; }
+    // apply to columns p+1..n-1, then downdate their norms (one column per lane)
+    const int j = lane;
+    if (j > p && j < n) {
+      if (len == 1) {
+        qr[p + j * m] *= (1 - tau);
+      } else if (tau != 0) {
+        double tmp = 0;
+        for (int i = 1; i < len; i++) tmp += qr[p + i + p * m] * qr[p + i + j * m];
+        tmp += qr[p + j * m];
+        qr[p + j * m] -= tau * tmp;
+        for (int i = 1; i < len; i++) qr[p + i + j * m] -= tau * qr[p + i + p * m] * tmp;
+      }
+      if (nu[j] != 0) {
+        double temp = fabs(qr[p + j * m]) / nu[j];
+        temp = (1 + temp) * (1 - temp);
+        temp = temp < 0 ? 0 : temp;
+        const double ratio = nu[j] / nd[j];
+        const double temp2 = temp * (ratio * ratio);
+        if (temp2 <= ndt) {
+          double s = 0;
+          for (int i = p + 1; i < m; i++) s += qr[i + j * m] * qr[i + j * m];
+          nd[j] = sqrt(s);
+          nu[j] = nd[j];
+        } else {
+          nu[j] *= sqrt(temp);
+        }
+      }
+    }
+    wave_sync();
+  }
+  np = __builtin_amdgcn_readfirstlane(np);
+  // solve: c = Q^T u (the first np reflections), R z = c, B.row(i)[perm[k]] = z[k]; lane = right-hand side
+  const int i = lane;
+  for (int p = 0; p < np; p++) {
+    const int len = m - p;
+    const double tau = hc[p];
+    if (i < cfg) {
+      if (len == 1) {
+        C[p * cfg + i] *= (1 - tau);
+      } else if (tau != 0) {
+        double tmp = 0;
+        for (int r = 1; r < len; r++) tmp += qr[p + r + p * m] * C[(p + r) * cfg + i];
+        tmp += C[p * cfg + i];
+        C[p * cfg + i] -= tau * tmp;
+        for (int r = 1; r < len; r++) C[(p + r) * cfg + i] -= tau * qr[p + r + p * m] * tmp;
+      }
+    }
+  }
+  for (int r = np - 1; r >= 0; r--) {
+    if (i < cfg) {
+      double x = C[r * cfg + i];
+      for (int j = r + 1; j < np; j++) x -= qr[r + j * m] * C[j * cfg + i];
+      C[r * cfg + i] = x / qr[r + r * m];
+    }
+  }
+  wave_sync();
+  for (int k = 0; k < n; k++) {
+    const int col = perm[k];
+    if (col < nmj && i < cfg) bt[(size_t)col * cfg + i] = (k < np) ? C[k * cfg + i] : 0.0;
+  }
+  if (lane == 0) rank[b] = np;
+}
+
+// the fp64 probe kernel is held to the 2-waves/SIMD budget, like the trial kernel
+template <int NM, int MM, class R, class S>
+static void launch_probe_class(const hs_topo* d_topo, const S* d_sim, const hs_sim_probe_kargs& ka, hipStream_t st) {
+  constexpr int MINW = sizeof(R) == 8 ? 2 : 1;
+  hipLaunchKernelGGL((hs_sim_kernel<NM, MM, R, MINW, false, true>), dim3(ka.sim.n_rollouts * ka.m), dim3(WAVE), 0, st,
+                     d_topo, d_sim, ka);
+}
+
+template <class R, class S>
+static int launch_probe_typed(const hs_topo* d_topo, const S* d_sim, const hs_simtopo& hs, const hs_sim_probe_kargs& ka) {
+  hipStream_t st = (hipStream_t)ka.sim.stream;
+  // the LDS classes of hs_sim_step
+  if (hs.n <= 18 && hs.m_max <= 144)
+    launch_probe_class<18, 144, R>(d_topo, d_sim, ka, st);
+  else if (hs.n <= 22 && hs.m_max <= 176)
+    launch_probe_class<22, 176, R>(d_topo, d_sim, ka, st);
+  else if (hs.n <= HS_NMAX && hs.m_max <= 9 * HS_NMAX)
+    launch_probe_class<HS_NMAX, 9 * HS_NMAX, R>(d_topo, d_sim, ka, st);
+  else
+    return (int)hipErrorInvalidValue;
+  return (int)hipGetLastError();
+}
+
+}  // namespace
+
+namespace hs {
+
+int launch_sim_config(const hs_topo* d_topo, const hs_simtopo* d_sim, const hs_simtopo_t<float>* d_sim_f32, int32_t n,
+                      const double* body, double* config, int32_t config_stride, int32_t precision, void* stream) {
+  if (n <= 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((n + WAVE - 1) / WAVE);
+  if (precision == HS_PREC_F32)
+    hipLaunchKernelGGL(hs_sim_config_kernel<float>, grid, dim3(WAVE), 0, st, d_topo, d_sim_f32, n,
+                       reinterpret_cast<const float*>(body), reinterpret_cast<float*>(config), config_stride);
+  else
+    hipLaunchKernelGGL(hs_sim_config_kernel<double>, grid, dim3(WAVE), 0, st, d_topo, d_sim, n, body, config,
+                       config_stride);
+  return (int)hipGetLastError();
+}
+
+int launch_track_push(int32_t n, int32_t cfg, const double* config, int32_t config_stride, double dt, double* ders,
+                      void* stream) {
+  if (n <= 0) return 0;
+  const long total = (long)n * cfg;
+  hipLaunchKernelGGL(hs_track_push_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n,
+                     cfg, config, config_stride, 1. / dt, ders);
+  return (int)hipGetLastError();
+}
+
+int launch_sim_probe(const hs_topo* d_topo, const hs_simtopo* d_sim, const hs_simtopo_t<float>* d_sim_f32,
+                     const hs_simtopo& hs, const hs_sim_probe_kargs& a) {
+  if (a.sim.n_rollouts <= 0 || a.m <= 0) return 0;
+  if (a.sim.precision == HS_PREC_F32) return launch_probe_typed<float>(d_topo, d_sim_f32, hs, a);
+  return launch_probe_typed<double>(d_topo, d_sim, hs, a);
+}
+
+int launch_probe_accel(int32_t n, int32_t m, int32_t cfg, const double* config_out, const double* ders, double dt,
+                       double* U, void* stream) {
+  if (n <= 0 || m <= 0) return 0;
+  const long total = (long)n * m * cfg;
+  hipLaunchKernelGGL(hs_probe_accel_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n,
+                     m, cfg, config_out, ders, 1. / dt, U);
+  return (int)hipGetLastError();
+}
+
+size_t regress_lds_bytes(int32_t m, int32_t nmj, int32_t cfg) {
+  const size_t n = (size_t)nmj + 1;
+  return ((size_t)m * n + (size_t)m * cfg + 3 * n) * sizeof(double) + n * sizeof(int);
+}
+
+int launch_regress_B(int32_t n, int32_t m, int32_t nmj, int32_t cfg, const double* T, const double* U, double* Bt,
+                     int32_t* rank, void* stream) {
+  if (n <= 0) return 0;
+  const size_t lds = m > 0 ? regress_lds_bytes(m, nmj, cfg) : 0;
+  hipLaunchKernelGGL(hs_regress_kernel, dim3(n), dim3(WAVE), lds, (hipStream_t)stream, n, m, nmj, cfg, T, U, Bt, rank);
+  return (int)hipGetLastError();
+}
+
+}  // namespace hs

@@ -110,3 +110,20 @@ def gen_kicks(B: int, lo: float, hi: float, plane: str = "xz", seed: int = SEED,
     dv[:, 0] = mag * np.cos(th)
     dv[:, 2 if plane == "xz" else 1] = mag * np.sin(th)
     return dv
+
+
+def gen_torque_perturbations(B: int, m: int, nmj: int, del_torque: float = 0.4, seed: int = 0,
+                             id0: int = 0) -> np.ndarray:
+    """Torque perturbations [B][m][nmj] for SimBatch.probe / estimate_B, from the distribution of
+    estimate_B_by_regression (player.cpp:562-567): float(k - 50) / 50. * del_torque with k uniform in
+    0..99, i.e. 100 levels in [-del_torque, +0.98 del_torque]. The reference draws k from libc's rand(),
+    which is not restated; here entry (rollout id, probe, motor) is a counter hash (stream 8 of the
+    rollout's counter), so a slice of the batch (id0) or fewer probes give the same numbers."""
+    ids = np.arange(id0, id0 + B, dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        base = _splitmix(np.uint64(seed) + ids * np.uint64(16) + np.uint64(8))
+        j = np.arange(m, dtype=np.uint64)[None, :, None] << np.uint64(16)
+        k = np.arange(nmj, dtype=np.uint64)[None, None, :]
+        z = _splitmix(base[:, None, None] + (j | k))
+    level = ((z >> np.uint64(11)).astype(np.float64) * (100.0 / 9007199254740992.0)).astype(np.int64)
+    return (level - 50).astype(np.float64) / 50. * del_torque

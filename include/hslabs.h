@@ -14,6 +14,7 @@
  */
 #ifndef HSLABS_H
 #define HSLABS_H
+#include <stddef.h>
 #include <stdint.h>
 #ifdef __cplusplus
 extern "C" {
@@ -578,6 +579,92 @@ typedef struct {
 
 /* Tally of state [n] (DEVICE) into *out_host (HOST); one reduction launch on stream, synchronous. */
 int hs_sim_trial_summary(const int32_t* state, int32_t n, hs_trial_summary* out_host, void* stream);
+
+/*
+ * Dynamics from simulation (additive exports: HSLABS_ABI_VERSION stays 16, no existing layout or
+ * meaning changes): modelplayer::estimate_B_by_regression (player.cpp:548-582), the first line of
+ * simulate_ode when dynamics_from_simulation_flag is set (player.cpp:327), for every rollout of a batch.
+ * The m one-step probe simulations of a rollout, which the reference runs one after another from a
+ * saved odestate, are m wavefronts of one launch. All arrays are DEVICE arrays; with HS_PREC_F32 the
+ * double* arrays hold floats, as in hs_sim_args.
+ */
+
+/* visualizer::get_ode_config (visualization.cpp:378-396) of n body states: torso translation ->
+ * config[0:3], euler_angles_from_affine of the torso pose -> config[3:6], dJointGetHingeAngle of every
+ * motor in motor order -> config[6:]. The inverse of hs_sim_reset. body [n][n_parts][HS_SIM_BODY_STRIDE],
+ * config [n][config_stride]. Deviation: the rotation of a body is dQtoR of its quaternion, also for a
+ * state that was just reset (ODE keeps the matrix dBodySetRotation was given until the first step). */
+int hs_sim_config(hs_model_t model, int32_t n, const double* body, double* config, int32_t config_stride,
+                  int32_t precision, void* stream);
+
+/* configtimedertrack(2, config_dim, dt)::push_config (odestate.cpp:105-119) of n trackers:
+ * ders [n][3][config_dim] = configuration, first and second backward difference, read and advanced.
+ * Level by level: subtract, then multiply by (1./dt). A tracker starts as zeros (odestate.cpp:93), so its
+ * first push yields config / dt as "velocity", like the reference; angles are not wrapped, like the
+ * reference. HS_PREC_F64 only (HS_E_ARG otherwise): the second difference divides rounding by dt^2. */
+int hs_sim_track_push(hs_model_t model, int32_t n, const double* config, int32_t config_stride, double dt,
+                      double* ders, int32_t precision, void* stream);
+
+/* The probe loop of estimate_B_by_regression (player.cpp:563-577). Probe j of rollout b starts from
+ * body[b] (read only: odestate::save / load), applies tau0[b] + dtau[b][j] as
+ * visualizer::set_ode_motor_torques does (no PD, no clip, no kick, no fall check), and takes one step of
+ * hs_sim_step's simulation. The perturbations are the caller's (the reference draws them with libc's
+ * rand(), player.cpp:567, which is not restated; hslabs_amd.synth.gen_torque_perturbations draws from the
+ * same distribution). dRand: odestate does not hold ODE's stream, so the reference's probes consume it in
+ * turn; probe j starts from seed[b] advanced by j steps' worth of draws (every probe of a rollout has the
+ * same contact set, hence the same number of draws), and seed[b] after the call is the seed after m probes. */
+typedef struct {
+  int32_t n_rollouts;
+  int32_t m;               /* probes per rollout; the reference's is config_dim + 20 */
+  int32_t precision;       /* HS_PREC_F64 or HS_PREC_F32 */
+  int32_t reserved;
+  hs_sim_params params;
+  const double* body;      /* [B][n_parts][HS_SIM_BODY_STRIDE], read only */
+  uint32_t* seed;          /* [B], read and advanced */
+  const double* tau0;      /* [B][nmj] last motor torques; NULL = zeros */
+  const double* dtau;      /* [B][m][nmj] perturbations */
+  double* config_out;      /* [B][m][config_dim] hs_sim_config of the stepped probe */
+  double* tau_out;         /* [B][m][nmj] torques applied, tau0 + dtau */
+  double* body_out;        /* optional [B][m][n_parts][HS_SIM_BODY_STRIDE] */
+  int32_t* n_contacts;     /* optional [B][m] */
+  void* stream;            /* hipStream_t */
+} hs_sim_probe_args;
+
+/* One launch of B * m wavefronts. HS_E_ARG for a NULL body, seed, dtau, config_out or tau_out, m < 0,
+ * and the parameter checks of hs_sim_step. m == 0 does nothing. */
+int hs_sim_probe(hs_model_t model, const hs_sim_probe_args* args);
+
+/* B_from_T_U (player.cpp:531-546) per rollout: A = [T^T | 1] (m x (nmj + 1)), Eigen 3.3
+ * ColPivHouseholderQR, B.row(i) = solve(U.row(i)^T) for the config_dim right-hand sides,
+ * Bt[b][j][:] = B.col(j) for j < nmj (the constant column is dropped). T [B][m][nmj], U [B][m][config_dim],
+ * Bt [B][nmj][config_dim], rank [B] = the nonzero pivots the solve used. m == 0: set_Bt_unity
+ * (player.cpp:522-529), rank 0. HS_E_ARG for NULL arrays, m < 0, HS_PREC_F32, a system too large for
+ * the kernel's 64 KB of LDS, and 0 < m < nmj + 1. Deviation: for the latter the reference returns Eigen's
+ * rank-deficient basic solution, which is not pinned here. */
+int hs_sim_regress_B(hs_model_t model, int32_t n, int32_t m, const double* T, const double* U, double* Bt,
+                     int32_t* rank, int32_t precision, void* stream);
+
+/* One estimate_B_by_regression for every rollout, in the reference's order: hs_sim_config of the
+ * current state; hs_sim_track_push into ders (player.cpp:557-558: the call advances the tracker);
+ * hs_sim_probe; U[b][j] = the second difference of a copy of tracker b after pushing config_out[b][j]
+ * (player.cpp:564, 572-575); hs_sim_regress_B with T = tau_out. The torques of the next real step are the
+ * caller's business, and so is tau0. */
+typedef struct {
+  hs_sim_probe_args probe; /* precision must be HS_PREC_F64; config_out and tau_out (= T) are required */
+  double* ders;            /* [B][3][config_dim], read and advanced */
+  double* U;               /* [B][m][config_dim] probe accelerations */
+  double* Bt;              /* [B][nmj][config_dim] */
+  int32_t* rank;           /* [B] */
+  void* workspace;         /* hs_sim_estimate_workspace(model, B, m) bytes, caller-owned, 8-byte aligned */
+  size_t workspace_bytes;
+} hs_sim_estimate_args;
+
+/* Bytes of workspace hs_sim_estimate_B needs (the current configuration and a copy of the seeds). */
+size_t hs_sim_estimate_workspace(hs_model_t model, int32_t n_rollouts, int32_t m);
+
+/* HS_E_ARG for everything hs_sim_probe and hs_sim_regress_B reject, a NULL ders, U, Bt, rank or
+ * workspace, and a workspace smaller than hs_sim_estimate_workspace. */
+int hs_sim_estimate_B(hs_model_t model, const hs_sim_estimate_args* args);
 
 /* Host-side handle over the calls above, for callers without device memory of their own
  * (the C++ shim's modelplayer): owns the device tables and state of B rollouts.
