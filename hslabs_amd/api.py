@@ -207,6 +207,11 @@ def limb_tile_launches() -> int:
     return int(capi.load().hs_limb_tile_launches())
 
 
+def limb_tile_plan_launches() -> int:
+    """those of limb_tile_launches() that ran the tile planner's slot sequence (hs_limb_tile_plan_launches)"""
+    return int(capi.load().hs_limb_tile_plan_launches())
+
+
 def limb_launches() -> int:
     """fused step launches this process made with the limb-lane kernel (hs_limb_launches)"""
     return int(capi.load().hs_limb_launches())

@@ -321,6 +321,7 @@ int launch_steps(const launch_ctx& cx, const hs_run_args& a, int32_t n_calls, vo
 
 std::atomic<int64_t> g_limb_launches{0};
 std::atomic<int64_t> g_limb_tile_launches{0};  // those of them on the tile mapping
+std::atomic<int64_t> g_limb_tile_plan_launches{0};  // those of these on the planner's slot sequence
 // hs_run_steps' calls up to this horizon take the online shapes (a launch per call holds the call's
 // horizon steps; longer calls keep hs_rollout_kernel's launch per step)
 #define HS_ONLINE_MAX_H 64
@@ -328,7 +329,7 @@ std::atomic<int64_t> g_limb_tile_launches{0};  // those of them on the tile mapp
 // A switch of the step kernels' routing, read from the environment on every call (a test switches kernels
 // within one process): one that is on by default is off at a value starting with 0, one that is off by
 // default is on at a value starting with 1. HS_LIMB (on), HS_LIMB_F32 (on), HS_LIMB_ONLINE (off),
-// HS_ONLINE_DEFER (off), HS_FIX_BARRIER (on), HS_LIMB_TILE (on).
+// HS_ONLINE_DEFER (off), HS_FIX_BARRIER (on), HS_LIMB_TILE (on), HS_LIMB_TILE_PLAN (on).
 bool env_switch(const char* name, bool on_by_default) {
   const char* e = getenv(name);
   if (!e) return on_by_default;
@@ -419,6 +420,18 @@ bool limb_tile(step_route rt, const hs_run_args& a, int32_t n) {
   const int32_t idle = HS_TILE_SLOTS * limb_tile_count(n) - n;
   return a.precision != HS_PREC_F32 && n >= HS_LIMB_TILE_MIN_STEPS && 32 * idle <= n;
 }
+// A tile-mapped launch's slot sequence (hs_limb_tile.h), launch_limb's tile_plan: 1, the planner's sequence
+// where it needs fewer FK passes than the parity order (a hexapod's 200-step launch: 5 instead of 15) and
+// the parity order elsewhere; HS_LIMB_TILE_PLAN=0 keeps the parity order everywhere (A/B runs), =2 takes
+// the planner's chain-aligned sequence even where it saves nothing (a four-limb model; the tests). The
+// outputs are the same bitwise under every sequence. Measured against the parent library, B = 4096, 9
+// interleaved rounds (profiles/limb_tile_plan_ab.txt): n = 200 +4.4 %, 64 +4.2 %, forces mode +3.0 % (each
+// clear of the spread), 40 +2.4 % (not clear), the mixed plan +0.2 % (inside the spread).
+int32_t limb_tile_plan_mode() {
+  if (!env_switch("HS_LIMB_TILE_PLAN", true)) return 0;
+  const char* e = getenv("HS_LIMB_TILE_PLAN");
+  return e && e[0] == '2' ? 2 : 1;
+}
 
 // Steps per fused launch: the launch refills the SIMDs from its queue of wavefronts (the batch's last
 // wavefronts no longer end every step). Up to 512k wavefronts per launch (256 rounds of a full
@@ -505,8 +518,6 @@ int run_fused(const launch_ctx& cx, const hs_run_args& a, int32_t n_calls, step_
   // (HS_FIX_BARRIER=0: each workgroup fixes its own rollouts' items, A/B)
   const bool barrier_ok = (B + 63) / 64 <= 1024 && env_switch("HS_FIX_BARRIER", true);
   mp.prep_unit = limb ? 8 : 2;  // the rollouts' records written on the XCD whose step launches read them
-  // the step launch (LIMB_ONLINE without the IK table is routed to hs_rollout_kernel's, the same shape)
-  const auto launch_step = limb ? k.launch_limb : k.launch_fused;
   int le = launch_setup(cx, c, mp);
   mp.red_total_mass = cx.total_mass;  // read by the launches with fix_reduce
   mp.red_rollout_mass = cx.rollout_mass;
@@ -524,9 +535,13 @@ int run_fused(const launch_ctx& cx, const hs_run_args& a, int32_t n_calls, step_
     mp.limb_tile = limb_tile(rt, a, mp.fused_n);
     hipError_t e = kernel_events ? hipEventRecord((hipEvent_t)kernel_events[2 * i], st) : hipSuccess;
     if (e != hipSuccess) return hip_fail(e, "hipEventRecord");
-    le = launch_step(cx.d_topo, c, cx.ws, mp);
+    int32_t planned = 0;
+    // the step launch (LIMB_ONLINE without the IK table is routed to hs_rollout_kernel's, the same shape)
+    le = limb ? k.launch_limb(cx.d_topo, c, cx.ws, mp, limb_tile_plan_mode(), &planned)
+              : k.launch_fused(cx.d_topo, c, cx.ws, mp);
     g_limb_launches += limb;
     g_limb_tile_launches += mp.limb_tile;
+    g_limb_tile_plan_launches += planned;
     if (le != 0) break;
     // the same steps' declined (step, rollout) items, with the general path; together with the work
     // reduce after every online call, else after the last step launch of an HS_SOLVE_AUTO call (few
@@ -576,6 +591,7 @@ int hs_model_limb_lane(hs_model_t m, int32_t* ok) {
 
 int64_t hs_limb_launches(void) { return g_limb_launches.load(); }
 int64_t hs_limb_tile_launches(void) { return g_limb_tile_launches.load(); }
+int64_t hs_limb_tile_plan_launches(void) { return g_limb_tile_plan_launches.load(); }
 
 int hs_limb_stats(int64_t* launches, int64_t* deferred) {
   if (launches) *launches = g_limb_launches.load();
@@ -797,9 +813,11 @@ int hs_run_forces_calls(hs_model_t m, const hs_run_args* a, int32_t n_calls, con
       mp.fix_count = fix_counts + ci;
       mp.fix_mode = hs::FIX_DEFER;
       mp.limb_tile = limb_tile(step_route::LIMB_FUSED, *a, mp.fused_n);
-      le = k.launch_limb(cx.d_topo, c, cx.ws, mp);
+      int32_t planned = 0;
+      le = k.launch_limb(cx.d_topo, c, cx.ws, mp, limb_tile_plan_mode(), &planned);
       g_limb_launches++;
       g_limb_tile_launches += mp.limb_tile;
+      g_limb_tile_plan_launches += planned;
       if (le != 0) break;
       mp.fix_mode = hs::FIX_SOLVE;
       mp.fix_reduce = 0;

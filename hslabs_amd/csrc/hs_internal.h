@@ -128,7 +128,10 @@ struct kernels {
   int (*launch_fused)(const hs_topo* d_topo, const hs_run_args& a, void* workspace, const launch_map& mp);
   // the same fused step launch by the limb-lane kernel (hs_limb.h): lane = (rollout, limb), 8 rollouts per
   // wavefront; the steps it does not take are deferred to the FIX_SOLVE launch like the fused launch's
-  int (*launch_limb)(const hs_topo* d_topo, const hs_run_args& a, void* workspace, const launch_map& mp);
+  // A tile-mapped launch (mp.limb_tile) takes its slot sequence from the planner (hs_limb_tile.h) at tile_plan
+  // 1 where that saves FK passes and at 2 always, else the parity order; *tile_planned: whether it did
+  int (*launch_limb)(const hs_topo* d_topo, const hs_run_args& a, void* workspace, const launch_map& mp,
+                     int32_t tile_plan, int32_t* tile_planned);
   // work_cot[b] = (w, w / (total_mass * step_length)) with w = (accumulate ? work_cot[b][0] : 0) + the steps'
   // work in step order, then the best key
   // (rollout_mass: per-rollout total mass of a mixed plan, else null and total_mass)

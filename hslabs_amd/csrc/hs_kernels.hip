@@ -3712,7 +3712,9 @@ static int launch_fused(const hs_topo* d_topo, const hs_run_args& a, void* works
   return (int)hipGetLastError();
 }
 
-static int launch_limb(const hs_topo* d_topo, const hs_run_args& a, void* workspace, const launch_map& mp) {
+static int launch_limb(const hs_topo* d_topo, const hs_run_args& a, void* workspace, const launch_map& mp,
+                       int32_t tile_plan, int32_t* tile_planned) {
+  if (tile_planned) *tile_planned = 0;
   if (a.n_rollouts <= 0 || mp.fused_n <= 0) return 0;
   hipStream_t st = (hipStream_t)a.stream;
   RolloutWS* ws = (RolloutWS*)workspace;
@@ -3721,21 +3723,40 @@ static int launch_limb(const hs_topo* d_topo, const hs_run_args& a, void* worksp
   const int vsteps = mp.limb_tile ? HS_TILE_SLOTS * limb_tile_count(mp.fused_n) : mp.fused_n;
   const dim3 grid((unsigned)((int64_t)m.fused_w * vsteps));
   const int nm = mp.max_parts <= 18 ? 18 : (mp.max_parts <= 22 ? 22 : HS_NMAX);
-#define HS_LIMB_LAUNCH(NM_, FORCES_, TILE_) \
-  hipLaunchKernelGGL((hs_limb_kernel<NM_, FORCES_, TILE_>), grid, dim3(WAVE), 0, st, d_topo, a, ws, m)
-#define HS_LIMB_LAUNCH_NM(FORCES_, TILE_)              \
-  do {                                                 \
-    if (nm == 18) HS_LIMB_LAUNCH(18, FORCES_, TILE_);  \
-    else if (nm == 22) HS_LIMB_LAUNCH(22, FORCES_, TILE_); \
-    else HS_LIMB_LAUNCH(HS_NMAX, FORCES_, TILE_);      \
-  } while (0)
-  if (mp.tau_in) {  // solve_forces (hs_run_forces_calls)
-    if (mp.limb_tile) HS_LIMB_LAUNCH_NM(true, true);
-    else HS_LIMB_LAUNCH_NM(true, false);
-  } else {
-    if (mp.limb_tile) HS_LIMB_LAUNCH_NM(false, true);
-    else HS_LIMB_LAUNCH_NM(false, false);
+  // the tile mapping's slot sequence (hs_limb_tile.h), a kernel argument: the planner's where it saves FK
+  // passes (tile_plan 1; 2: its chain-aligned sequence whatever it saves), else the parity order
+  // (n_slots = 0), as for every launch longer than a plan holds
+  limb_tile_plan_arg plan = {};
+  if (mp.limb_tile && tile_plan && mp.fused_n <= HS_TILE_PLAN_STEPS && mp.fused_h >= 1 && a.n_t >= 1 && a.k0 >= 0 &&
+      mp.fused_s0 >= 0) {
+    const limb_tile_launch L = {mp.fused_n, mp.fused_s0, mp.fused_h, a.k0, a.n_t, mp.ktab_nl > 0 ? mp.ktab_nl : HS_LMAX};
+    bool planned = true;
+    if (tile_plan == 2) {
+      int row[HS_TILE_PLAN_STEPS];
+      limb_tile_rows(L, row);
+      limb_tile_chain_fill(row, L.n, plan.step);
+    } else {
+      planned = limb_tile_plan(L, plan.step);
+    }
+    if (planned) plan.n_slots = vsteps;
+    if (tile_planned) *tile_planned = planned;
   }
+#define HS_LIMB_LAUNCH(NM_, FORCES_)                                                                                  \
+  do {                                                                                                                \
+    if (mp.limb_tile)                                                                                                 \
+      hipLaunchKernelGGL((hs_limb_kernel<NM_, FORCES_, true, limb_tile_plan_arg>), grid, dim3(WAVE), 0, st, d_topo, a, ws, \
+                         m, plan);                                                                                    \
+    else                                                                                                              \
+      hipLaunchKernelGGL((hs_limb_kernel<NM_, FORCES_, false>), grid, dim3(WAVE), 0, st, d_topo, a, ws, m);           \
+  } while (0)
+#define HS_LIMB_LAUNCH_NM(FORCES_)               \
+  do {                                           \
+    if (nm == 18) HS_LIMB_LAUNCH(18, FORCES_);   \
+    else if (nm == 22) HS_LIMB_LAUNCH(22, FORCES_); \
+    else HS_LIMB_LAUNCH(HS_NMAX, FORCES_);       \
+  } while (0)
+  if (mp.tau_in) HS_LIMB_LAUNCH_NM(true);  // solve_forces (hs_run_forces_calls)
+  else HS_LIMB_LAUNCH_NM(false);
 #undef HS_LIMB_LAUNCH_NM
 #undef HS_LIMB_LAUNCH
   return (int)hipGetLastError();

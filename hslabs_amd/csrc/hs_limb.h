@@ -392,9 +392,10 @@ __device__ __attribute__((always_inline)) inline void limb_forces(const hs_topo*
 #undef FDBG
 
 // ---- the tile mapping's K and D phase ----
-// A tile-mapped wavefront is one rollout x eight steps: group g runs local step limb_tile_step(8 tile + g),
-// two steps after group g - 1's wherever the slot sequence has no break, so its stencil rows t - 2dt and
-// t + 2dt are its neighbours' centre rows. Every limb lane runs the FK of its group's centre row only and
+// A tile-mapped wavefront is one rollout x eight steps: group g runs the local step of slot 8 tile + g of the
+// launch's sequence (hs_limb_tile.h), two rows after group g - 1's wherever the sequence has no break, so
+// its stencil rows t - 2dt and t + 2dt are its neighbours' centre rows. Every limb lane runs the FK of its
+// group's centre row only and
 // stores the links' pos / ust into the outer rows of the groups that read them (sh.k.outer, the packed
 // mapping's layout: the step's lanes read their own columns as before). A row no neighbour's centre holds
 // -- the minus row of the tile's first group, the plus row of its last, both sides of a break -- is a
@@ -650,9 +651,12 @@ __device__ __attribute__((always_inline)) inline void limb_tile_kd(
 // every lane of the group; a B_f near singular defers the step to the forces fixup launch)
 // TILE: the tile mapping (a wavefront = one rollout x eight steps, limb_tile_kd above); else a wavefront =
 // eight rollouts x one step
-template <int NM, bool FORCES, bool TILE = false>
+// PLAN: none, or with TILE the launch's slot sequence (limb_tile_plan_arg, hs_limb_tile.h), read from the
+// kernel argument segment
+template <int NM, bool FORCES, bool TILE = false, class... PLAN>
 __global__ __launch_bounds__(WAVE, HS_REAL_IS_FLOAT ? HS_LIMB_WAVES_F32 : HS_LIMB_WAVES) void hs_limb_kernel(const hs_topo* __restrict__ T0, hs_run_args a,
-                                                                      RolloutWS* __restrict__ rws, hs::launch_map mp) {
+                                                                      RolloutWS* __restrict__ rws, hs::launch_map mp, PLAN... plan) {
+  static_assert(sizeof...(PLAN) == (TILE ? 1 : 0), "the tile mapping takes the launch's plan, the packed mapping nothing");
   // the outer samples' pos / ust of every lane's links (kinematics), then the groups' exchange arrays:
   // 18 KB per wavefront, 8 per CU at 2 waves / SIMD
   // kinematics: the outer samples' pos / ust of every limb lane's links and the limbs' link records (read
@@ -691,9 +695,9 @@ __global__ __launch_bounds__(WAVE, HS_REAL_IS_FLOAT ? HS_LIMB_WAVES_F32 : HS_LIM
     // share target nor a request: its outer rows in LDS are never written, its finite differences and all
     // that follows are computed on whatever the LDS holds (possibly NaN), and nothing of it is stored or
     // counted (every store, atomic and fix item is gated on live)
-    const int slot0 = HS_TILE_SLOTS * (fstep / LGR), ls = limb_tile_step(slot0 + grp, mp.fused_n);
+    const int slot0 = HS_TILE_SLOTS * (fstep / LGR), ls = limb_tile_plan_step(plan..., slot0 + grp, mp.fused_n);
     live = ls >= 0;
-    fstep = live ? ls : limb_tile_step(slot0, mp.fused_n);
+    fstep = live ? ls : limb_tile_plan_step(plan..., slot0, mp.fused_n);
   }
   // an idle group computes a copy of a rollout of its wavefront's model and stores nothing
   const int bb = live || TILE ? b : (mp.limb_rollouts ? mp.limb_rollouts[q * LGR] : a.n_rollouts - 1);

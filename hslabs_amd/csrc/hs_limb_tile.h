@@ -1,13 +1,27 @@
 // hs_limb_tile.h -- the slot sequence of the limb-lane kernel's tile mapping (hs_limb.h, TILE).
 //
-// A tile-mapped launch of n local steps gives every rollout the slot sequence: all even local steps
-// ascending, then all odd ones. Tile t of a rollout is slots 8 t .. 8 t + 7, one slot per 8-lane group of
-// the wavefront; slots past the sequence are idle groups (in the last tile only). Consecutive slots are
-// two steps apart, so a group's stencil rows t - 2dt and t + 2dt are its neighbours' centre rows wherever
-// the table row advances with the step (the kernel tests the rows themselves, not this sequence).
+// Tile t of a rollout is slots 8 t .. 8 t + 7 of the launch's slot sequence, one slot per 8-lane group of
+// the wavefront; slots past the sequence are idle groups (in the last tile only). A group's stencil rows
+// t - 2dt and t + 2dt are its neighbours' centre rows wherever consecutive slots hold steps whose table
+// rows are 2 apart (the kernel tests the rows themselves, not the sequence, so any sequence gives the same
+// values). Every row no neighbour holds is a request (limb_tile_kd); the first E0 of a tile run beside the
+// centre rows, every further eight cost the wavefront one more FK pass.
 //
-// Plain C++: host code, device code and a CPU test include it.
+// Two sequences:
+//   the parity order (limb_tile_step): all even local steps ascending, then all odd ones. Consecutive
+//     slots are two steps apart, but the table row wraps with the gait period (n_t = 20: every 10 slots),
+//     and a wrap inside a tile is a break: 2 more requests.
+//   the plan (limb_tile_plan): the launch's steps cut into chains whose rows ascend by 2, every run of 8
+//     of a chain a tile of its own (2 requests), the chains' remainders packed into the remaining tiles
+//     with as few segments per tile as the greedy finds. Kept only where it needs fewer passes than the
+//     parity order under limb_tile_passes, the kernel's own request arithmetic.
+// Every sequence holds each local step in exactly one slot, fills limb_tile_count(n) tiles, has its idle
+// slots (-1) at the end of the last tile only, and so a live slot 0 in every tile.
+//
+// Plain C++ without allocation: host code, device code and the CPU tests include it.
 #pragma once
+
+#include <stdint.h>
 
 #if defined(__HIP__)
 #define HS_TILE_FN __host__ __device__ inline
@@ -20,9 +34,163 @@ constexpr int HS_TILE_SLOTS = 8;  // slots per tile: the 8-lane groups of a wave
 // tiles of a launch of n local steps
 HS_TILE_FN int limb_tile_count(int n) { return (n + HS_TILE_SLOTS - 1) / HS_TILE_SLOTS; }
 
-// the local step of a slot, -1 for a slot past the sequence
+// the parity order: the local step of a slot, -1 for a slot past the sequence
 HS_TILE_FN int limb_tile_step(int slot, int n) {
   const int n_even = (n + 1) / 2;
   if (slot < 0 || slot >= n) return -1;
   return slot < n_even ? 2 * slot : 2 * (slot - n_even) + 1;
+}
+
+// ---- the plan ----
+constexpr int HS_TILE_PLAN_STEPS = 256;  // the longest launch a plan holds (HS_FUSED_MAX_STEPS' default)
+
+// The planned slot sequence as the TILE kernels take it (a by-value kernel argument): n_slots =
+// 8 * limb_tile_count(n) when step[] holds a plan, 0 for the parity order.
+struct limb_tile_plan_arg {
+  int32_t n_slots;
+  int16_t step[HS_TILE_PLAN_STEPS];
+};
+// the local step of a slot under the launch's sequence
+HS_TILE_FN int limb_tile_plan_step(const limb_tile_plan_arg& p, int slot, int n) {
+  if (p.n_slots == 0) return limb_tile_step(slot, n);
+  return slot >= 0 && slot < p.n_slots ? p.step[slot] : -1;
+}
+
+// a launch as the planner sees it: n local steps from global step s0 of calls of h steps, the call's
+// k0 and n_t, and the limb lanes of a group (the launch's largest model)
+struct limb_tile_launch {
+  int n, s0, h, k0, n_t, n_limbs;
+};
+
+// the table row of a local step as hs_limb_kernel forms it, less the launch's constant ktab_lo
+HS_TILE_FN int limb_tile_row(const limb_tile_launch& L, int step) {
+  const int s_glob = L.s0 + step, call = s_glob / L.h;
+  return (int)(((int64_t)L.k0 + (int64_t)call * L.h) % L.n_t) + s_glob % L.h;
+}
+// row[i] = limb_tile_row(L, i) of the launch's n steps, stepping the call and its first row along
+HS_TILE_FN void limb_tile_rows(const limb_tile_launch& L, int* row) {
+  const int call = L.s0 / L.h, hm = L.h % L.n_t;
+  int pos = L.s0 % L.h, base = (int)(((int64_t)L.k0 + (int64_t)call * L.h) % L.n_t);
+  for (int i = 0; i < L.n; i++) {
+    row[i] = base + pos;
+    if (++pos == L.h) {
+      pos = 0;
+      base += hm;
+      if (base >= L.n_t) base -= L.n_t;
+    }
+  }
+}
+
+// requests the first pass serves on the lanes idle in every group (limb_tile_kd's E0)
+HS_TILE_FN int limb_tile_e0(int n_limbs) {
+  return n_limbs > 0 && n_limbs < HS_TILE_SLOTS ? HS_TILE_SLOTS * (HS_TILE_SLOTS - n_limbs) / n_limbs : 0;
+}
+
+// limb_tile_kd's requests of one tile (row[]: the launch's limb_tile_rows): a live slot's minus (plus) row
+// is shared only with the live slot before (after) it in the tile whose row is exactly 2 lower (higher);
+// every other one is a request
+HS_TILE_FN int limb_tile_requests(const int* row, const int16_t* slots) {
+  int req = 0;
+  for (int g = 0; g < HS_TILE_SLOTS; g++) {
+    if (slots[g] < 0) continue;
+    const int r = row[slots[g]];
+    const bool shm = g > 0 && slots[g - 1] >= 0 && row[slots[g - 1]] + 2 == r;
+    const bool shp = g < HS_TILE_SLOTS - 1 && slots[g + 1] >= 0 && row[slots[g + 1]] == r + 2;
+    req += !shm + !shp;
+  }
+  return req;
+}
+
+// the further FK passes of a tile with `req` requests, and of a launch's whole sequence
+HS_TILE_FN int limb_tile_req_passes(int req, int n_limbs) {
+  const int over = req - limb_tile_e0(n_limbs);
+  return over > 0 ? (over + HS_TILE_SLOTS - 1) / HS_TILE_SLOTS : 0;
+}
+HS_TILE_FN int limb_tile_passes(const int* row, int n, int n_limbs, const int16_t* step) {
+  int passes = 0;
+  for (int t = 0; t < limb_tile_count(n); t++)
+    passes += limb_tile_req_passes(limb_tile_requests(row, step + HS_TILE_SLOTS * t), n_limbs);
+  return passes;
+}
+HS_TILE_FN int limb_tile_passes(const limb_tile_launch& L, const int16_t* step) {  // (n <= HS_TILE_PLAN_STEPS)
+  int row[HS_TILE_PLAN_STEPS];
+  limb_tile_rows(L, row);
+  return limb_tile_passes(row, L.n, L.n_limbs, step);
+}
+
+// step[8 * limb_tile_count(n)] = the parity order
+HS_TILE_FN void limb_tile_parity_fill(int n, int16_t* step) {
+  for (int s = 0; s < HS_TILE_SLOTS * limb_tile_count(n); s++) step[s] = (int16_t)limb_tile_step(s, n);
+}
+
+// step[8 * limb_tile_count(n)] = the chain-aligned sequence (1 <= n <= HS_TILE_PLAN_STEPS): every run of
+// 8 of a chain in a tile of its own, in chain order; then the remainders (1 .. 7 steps each), a tile at a
+// time: the longest that still fits until the tile is full, and where none fits the head of the shortest
+// one left (a split, only to keep the tile count)
+HS_TILE_FN void limb_tile_chain_fill(const int* row, int n, int16_t* step) {
+  const int n_slots = HS_TILE_SLOTS * limb_tile_count(n);
+  // the remainders, listed by length in chain order: first step rem0[], the next of the same length nxt[]
+  // (a record per remainder and per split, at most one split a tile)
+  constexpr int NREC = HS_TILE_PLAN_STEPS + HS_TILE_PLAN_STEPS / HS_TILE_SLOTS;
+  int16_t rem0[NREC], nxt[NREC];
+  int head[HS_TILE_SLOTS], tail[HS_TILE_SLOTS], n_rem = 0, out = 0;
+  for (int k = 0; k < HS_TILE_SLOTS; k++) head[k] = tail[k] = -1;
+  auto push = [&](int first, int len) {
+    rem0[n_rem] = (int16_t)first;
+    nxt[n_rem] = -1;
+    if (tail[len] < 0) head[len] = n_rem;
+    else nxt[tail[len]] = (int16_t)n_rem;
+    tail[len] = n_rem++;
+  };
+  for (int i = 0; i < n; i++) {
+    if (i >= 2 && row[i - 2] + 2 == row[i]) continue;  // inside a chain
+    int len = 1;
+    while (i + 2 * len < n && row[i + 2 * len - 2] + 2 == row[i + 2 * len]) len++;
+    const int full = len / HS_TILE_SLOTS * HS_TILE_SLOTS;
+    for (int j = 0; j < full; j++) step[out++] = (int16_t)(i + 2 * j);
+    if (len > full) push(i + 2 * full, len - full);
+  }
+  while (out < n) {
+    int cap = n - out < HS_TILE_SLOTS ? n - out : HS_TILE_SLOTS;
+    while (cap > 0) {
+      int len = cap < HS_TILE_SLOTS - 1 ? cap : HS_TILE_SLOTS - 1;
+      while (len > 0 && head[len] < 0) len--;
+      int take = len;
+      if (len == 0) {  // every remainder left is longer than the tile's room: split the shortest
+        for (len = cap + 1; head[len] < 0; len++) {}
+        take = cap;
+      }
+      const int r = head[len], first = rem0[r];
+      head[len] = nxt[r];
+      if (head[len] < 0) tail[len] = -1;
+      for (int j = 0; j < take; j++) step[out++] = (int16_t)(first + 2 * j);
+      if (len > take) push(first + 2 * take, len - take);
+      cap -= take;
+    }
+  }
+  for (; out < n_slots; out++) step[out] = -1;
+}
+
+// The launch's sequence: the chain-aligned one where it needs fewer passes than the parity order, else
+// the parity order. Returns whether step[] holds the former. A launch longer than a plan holds keeps the
+// parity order (step[] is then not written: the caller uses limb_tile_step).
+// *passes / *parity_passes: the further FK passes of the sequence kept and of the parity order.
+HS_TILE_FN bool limb_tile_plan(const limb_tile_launch& L, int16_t* step, int* passes = nullptr,
+                               int* parity_passes = nullptr) {
+  if (L.n < 1 || L.n > HS_TILE_PLAN_STEPS || L.h < 1 || L.n_t < 1 || L.k0 < 0 || L.s0 < 0) return false;
+  int16_t par[HS_TILE_PLAN_STEPS];
+  int row[HS_TILE_PLAN_STEPS];
+  limb_tile_rows(L, row);
+  limb_tile_parity_fill(L.n, par);
+  const int pp = limb_tile_passes(row, L.n, L.n_limbs, par);
+  int pc = pp;
+  if (pp > 0) {  // (nothing to save otherwise: a four-limb model's E0 = 8 takes every request of most tiles)
+    limb_tile_chain_fill(row, L.n, step);
+    pc = limb_tile_passes(row, L.n, L.n_limbs, step);
+  }
+  if (parity_passes) *parity_passes = pp;
+  if (passes) *passes = pc < pp ? pc : pp;
+  if (pc < pp) return true;
+  for (int s = 0; s < HS_TILE_SLOTS * limb_tile_count(L.n); s++) step[s] = par[s];
+  return false;
 }

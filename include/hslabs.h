@@ -704,10 +704,17 @@ void hs_sim_free(hs_sim_t sim);
  * packed; HS_LIMB_TILE_MIN=<n> (a positive decimal number, else ignored) replaces the rule by "at least
  * <n> steps" for every precision -- a test and measurement switch, slower than the rule where the rule
  * says packed. hs_limb_tile_launches: the limb-lane launches of this process that ran the tile mapping
- * (an additive export: HSLABS_ABI_VERSION stays 16, no existing layout or meaning changes). */
+ * (an additive export: HSLABS_ABI_VERSION stays 16, no existing layout or meaning changes).
+ * A tile-mapped launch of up to 256 steps orders its steps over the tiles by a planner (chains of steps
+ * whose table rows ascend by 2, a tile per run of 8) where that saves limb FK passes over the order "even
+ * steps, then odd steps", which it keeps elsewhere; the outputs are the same bitwise under either.
+ * HS_LIMB_TILE_PLAN=0 keeps the even/odd order everywhere, =2 takes the planner's order even where it saves
+ * nothing (tests). hs_limb_tile_plan_launches: the tile-mapped launches that ran the planner's order (an
+ * additive export as well). */
 int hs_model_limb_lane(hs_model_t model, int32_t* ok);
 int64_t hs_limb_launches(void);
 int64_t hs_limb_tile_launches(void);
+int64_t hs_limb_tile_plan_launches(void);
 /* Diagnostics of the limb-lane kernel: its launches and the steps it deferred to the fixup launch (one,
  * two contacts, guards near their thresholds, ...) in this process; *deferred is read from the device
  * (synchronous on the current device). Either pointer may be NULL. */

@@ -4,7 +4,11 @@ mean / p50 / p90 cycles per phase over the wavefronts of one window of the launc
 s * 512). Tuning aid only.   python tools/limb_stamps.py [--build] [--steps K] [--tile]
 --steps K: K calls instead of 20. --tile: the tile mapping at any K (HS_LIMB_TILE_MIN=1), its phases named
 as limb_tile_kd stamps them: the one FK pass (centre rows and the first requests), the further passes
-(taken at a break of the slot sequence), the exchange's barrier with the finite differences."""
+(taken at a break of the slot sequence), the exchange's barrier with the finite differences.
+--tile --passes: instead of one window's phases, the share of the launch's tile wavefronts that take further FK
+passes, from windows over the whole launch (the planner, hs_limb_tile.h, puts the tiles of chain remainders last,
+so no single window shows it; HS_LIMB_TILE_PLAN=0 for the parity order). A wavefront counts as taking them when
+its "further FK passes" phase lasts more than half its pass 0."""
 import ctypes
 import os
 import sys
@@ -51,6 +55,8 @@ def main():
     b = H.DeviceBatch(m, params, n_t=20, k0=0, horizon=K, outputs=("tau", "cf", "work_cot", "flags"))
     b.run_calls(K, best=True)
     torch.cuda.synchronize()
+    if tile and "--passes" in sys.argv:
+        return passes_share(L, b, K, n)
     L.hs_debug_set_stamp_base(ctypes.c_uint(int(os.environ.get("STEP", "4")) * (n // 8)))
     L.hs_debug_clear_stamps()
     b.run_calls(K, best=True)
@@ -67,6 +73,31 @@ def main():
     print(f"{'wave life (us)':28s} mean {d.mean():9.2f}  p50 {np.median(d):9.2f}  p90 {np.percentile(d, 90):9.2f}")
     s0 = (st[:, 16] - t0) / 100.0
     print(f"{'wave start (us)':28s} mean {s0.mean():9.2f}  max {s0.max():9.2f}")
+
+
+def passes_share(L, b, K, n):
+    """windows of 4096 blocks over the launch's (n / 8) * 8 * tiles blocks, a run each"""
+    import torch
+
+    blocks = (n // 8) * 8 * ((K + 7) // 8)
+    took = total = 0
+    extra = []
+    for base in range(0, blocks, 4096):
+        L.hs_debug_set_stamp_base(ctypes.c_uint(base))
+        L.hs_debug_clear_stamps()
+        b.run_calls(K, best=True)
+        torch.cuda.synchronize()
+        st = np.zeros((4096, 32), dtype=np.uint64)
+        L.hs_debug_read_stamps(st.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong)), 4096)
+        st = st.astype(np.int64)
+        st = st[(st[:, 9] != 0) & (st[:, 15] != 0)]
+        p0, further = st[:, 1] - st[:, 0], st[:, 2] - st[:, 1]
+        hit = further > p0 // 2
+        took += int(hit.sum())
+        total += len(st)
+        extra.extend(further[hit].tolist())
+    print(f"K = {K}: {took} of {total} tile wavefronts take further FK passes ({100.0 * took / max(total, 1):.1f} %), "
+          f"their further-passes phase p50 {np.median(extra) if extra else 0:.0f} cycles")
 
 
 if __name__ == "__main__":
