@@ -212,6 +212,11 @@ def limb_tile_plan_launches() -> int:
     return int(capi.load().hs_limb_tile_plan_launches())
 
 
+def limb_tile_loop_launches() -> int:
+    """those of limb_tile_launches() whose wavefronts ran more than one tile each (hs_limb_tile_loop_launches)"""
+    return int(capi.load().hs_limb_tile_loop_launches())
+
+
 def limb_launches() -> int:
     """fused step launches this process made with the limb-lane kernel (hs_limb_launches)"""
     return int(capi.load().hs_limb_launches())

@@ -322,6 +322,7 @@ int launch_steps(const launch_ctx& cx, const hs_run_args& a, int32_t n_calls, vo
 std::atomic<int64_t> g_limb_launches{0};
 std::atomic<int64_t> g_limb_tile_launches{0};  // those of them on the tile mapping
 std::atomic<int64_t> g_limb_tile_plan_launches{0};  // those of these on the planner's slot sequence
+std::atomic<int64_t> g_limb_tile_loop_launches{0};  // those of the tile-mapped ones with more than one tile per wavefront
 // hs_run_steps' calls up to this horizon take the online shapes (a launch per call holds the call's
 // horizon steps; longer calls keep hs_rollout_kernel's launch per step)
 #define HS_ONLINE_MAX_H 64
@@ -329,7 +330,8 @@ std::atomic<int64_t> g_limb_tile_plan_launches{0};  // those of these on the pla
 // A switch of the step kernels' routing, read from the environment on every call (a test switches kernels
 // within one process): one that is on by default is off at a value starting with 0, one that is off by
 // default is on at a value starting with 1. HS_LIMB (on), HS_LIMB_F32 (on), HS_LIMB_ONLINE (off),
-// HS_ONLINE_DEFER (off), HS_FIX_BARRIER (on), HS_LIMB_TILE (on), HS_LIMB_TILE_PLAN (on).
+// HS_ONLINE_DEFER (off), HS_FIX_BARRIER (on), HS_LIMB_TILE (on), HS_LIMB_TILE_PLAN (on). (HS_LIMB_TILE_MIN and
+// HS_LIMB_TILE_LOOP take numbers: limb_tile(), limb_tile_loop().)
 bool env_switch(const char* name, bool on_by_default) {
   const char* e = getenv(name);
   if (!e) return on_by_default;
@@ -432,6 +434,43 @@ int32_t limb_tile_plan_mode() {
   const char* e = getenv("HS_LIMB_TILE_PLAN");
   return e && e[0] == '2' ? 2 : 1;
 }
+// The tile loop (launch_map::limb_tile_loop): how many tiles of its rollout a tile-mapped wavefront runs one
+// after the other, so that the rollout's part of the step (its record's first-touch loads, the link records'
+// copy into LDS, a wavefront's start and end) is paid once per chunk of tiles. HS_LIMB_TILE_LOOP=<n> in the
+// environment (a positive decimal number; anything else is ignored), read per launch, forces n tiles per
+// wavefront, 1 a tile per wavefront (the tests and the A/B). The outputs are the same bitwise at every n.
+// Forces mode does not loop (hs_limb.h: its instantiations spill with the loop around them).
+// The rule, from measurement against the parent library (hexapod, B = 4096, 200 steps = 25 tiles, interleaved
+// rounds on one box, profiles/limb_tile_loop_ab.txt): 1 tile per wavefront -1.4 % (the loop's kernel without
+// its gain), 2 +2.1 %, 3 +4.8 %, 4 +5.0 %, 5 +4.2 / +4.4 %, 7 +4.6 %, 9 +4.6 %, 13 +3.3 %, 25 +2.2 %; at
+// B = 5000 (2.4 rounds of the chip's 2,048 resident wavefronts per tile) 2 +3.7 %, 3 +4.0 %, 5 +4.0 %, 13 +3.3 %,
+// 25 -2.0 % (one chunk per rollout: the last half round's wavefronts run 25 tiles with the chip half empty).
+// 3 to 9 tiles are one plateau within the spread; the rule takes 5, the middle of it. The queue bound: the
+// launch must keep chunks x rollouts >= 4 rounds of 2,048 wavefronts -- the shallowest queue measured to gain
+// (13 tiles: 2 chunks x 4096 = 4 rounds, 2 x 5000 = 4.9) where the next shallower loses (25 tiles: 2 and 2.4
+// rounds) -- else fewer tiles per wavefront; the tiles are then spread evenly over the chunks that remain (5
+// tiles in 2 chunks: 3 + 2, not 4 + 1). The rule as it stands, 9 rounds at B = 4096: 200 steps (5 tiles each)
+// +4.5 % clear, 64 steps (8 tiles: 2 chunks of 4, exactly 4 rounds) +1.9 % clear, 40 steps (5 tiles: 3 + 2)
+// +1.8 % not clear of the spread; B = 5000 +3.1 % clear. Batches other than 4096 and 5000 and the bound between
+// 2.4 and 4 rounds are EXTRAPOLATION, not measurement. Where the rule ends at 1 (a small batch: under 631
+// rollouts at 200 steps) the launch runs the loop's kernel without its gain, the -1.4 % above.
+#ifndef HS_LIMB_TILE_LOOP_TILES
+#define HS_LIMB_TILE_LOOP_TILES 5
+#endif
+#ifndef HS_LIMB_TILE_LOOP_ROUNDS
+#define HS_LIMB_TILE_LOOP_ROUNDS 4
+#endif
+constexpr int64_t HS_RESIDENT_LIMB_WAVES = 2048;  // 256 CUs x 4 SIMDs x 2 waves
+int32_t limb_tile_loop(const hs_run_args& a, int32_t n) {
+  const int32_t nt = limb_tile_count(n);
+  if (a.precision == HS_PREC_F32) return 1;  // the fp32 TILE instantiations have no tile loop (hs_limb.h)
+  if (const char* e = getenv("HS_LIMB_TILE_LOOP")) {
+    char* end = nullptr;
+    const long tl = strtol(e, &end, 10);
+    if (end != e && *end == '\0' && tl >= 1) return (int32_t)std::min<long>(tl, HS_TILE_PLAN_STEPS);
+  }
+  return limb_tile_loop_rule(nt, a.n_rollouts, HS_LIMB_TILE_LOOP_TILES, HS_LIMB_TILE_LOOP_ROUNDS * HS_RESIDENT_LIMB_WAVES);
+}
 
 // Steps per fused launch: the launch refills the SIMDs from its queue of wavefronts (the batch's last
 // wavefronts no longer end every step). Up to 512k wavefronts per launch (256 rounds of a full
@@ -533,6 +572,7 @@ int run_fused(const launch_ctx& cx, const hs_run_args& a, int32_t n_calls, step_
     mp.fix_count = fix_counts + i;
     mp.fix_reduce = 0;
     mp.limb_tile = limb_tile(rt, a, mp.fused_n);
+    mp.limb_tile_loop = mp.limb_tile ? limb_tile_loop(a, mp.fused_n) : 1;
     hipError_t e = kernel_events ? hipEventRecord((hipEvent_t)kernel_events[2 * i], st) : hipSuccess;
     if (e != hipSuccess) return hip_fail(e, "hipEventRecord");
     int32_t planned = 0;
@@ -542,6 +582,7 @@ int run_fused(const launch_ctx& cx, const hs_run_args& a, int32_t n_calls, step_
     g_limb_launches += limb;
     g_limb_tile_launches += mp.limb_tile;
     g_limb_tile_plan_launches += planned;
+    g_limb_tile_loop_launches += mp.limb_tile && std::min(mp.limb_tile_loop, limb_tile_count(mp.fused_n)) > 1;
     if (le != 0) break;
     // the same steps' declined (step, rollout) items, with the general path; together with the work
     // reduce after every online call, else after the last step launch of an HS_SOLVE_AUTO call (few
@@ -592,6 +633,7 @@ int hs_model_limb_lane(hs_model_t m, int32_t* ok) {
 int64_t hs_limb_launches(void) { return g_limb_launches.load(); }
 int64_t hs_limb_tile_launches(void) { return g_limb_tile_launches.load(); }
 int64_t hs_limb_tile_plan_launches(void) { return g_limb_tile_plan_launches.load(); }
+int64_t hs_limb_tile_loop_launches(void) { return g_limb_tile_loop_launches.load(); }
 
 int hs_limb_stats(int64_t* launches, int64_t* deferred) {
   if (launches) *launches = g_limb_launches.load();
@@ -813,6 +855,7 @@ int hs_run_forces_calls(hs_model_t m, const hs_run_args* a, int32_t n_calls, con
       mp.fix_count = fix_counts + ci;
       mp.fix_mode = hs::FIX_DEFER;
       mp.limb_tile = limb_tile(step_route::LIMB_FUSED, *a, mp.fused_n);
+      mp.limb_tile_loop = 1;  // forces mode runs a tile per wavefront (hs_limb.h: its instantiations have no tile loop)
       int32_t planned = 0;
       le = k.launch_limb(cx.d_topo, c, cx.ws, mp, limb_tile_plan_mode(), &planned);
       g_limb_launches++;

@@ -106,6 +106,10 @@ struct launch_map {
   // grid is limb wavefronts x 8 * limb_tile_count(fused_n) blocks, block -> (virtual step v, batch wavefront
   // w) by fused_coords, rollout 8 w + v % 8 (limb_rollouts[...] in a mixed plan), tile v / 8
   int32_t limb_tile;
+  // tiles a tile-mapped wavefront runs one after the other (the tile loop, hs_limb_tile.h; below 1 counts as
+  // 1): the launch's tiles are cut into ceil(tiles / limb_tile_loop) chunks, the grid is limb wavefronts x 8 x
+  // chunks, and the virtual step v above is (chunk v / 8, rollout v % 8). 1: a tile per wavefront
+  int32_t limb_tile_loop;
 };
 
 // one fused step's general-path scratch per rollout (fused_gen holds [steps in a launch][B + 1] of them)

@@ -319,10 +319,13 @@ __device__ inline void gsync() {
 // (slots 16, 17: the constant 100 MHz clock at wave entry and exit, comparable across CUs)
 __device__ unsigned long long g_stamps[4096][32];  // slots 24..31: hs_prep_kernel's
 __device__ unsigned int g_stamp_base;  // row r holds block g_stamp_base + r (hs_debug_set_stamp_base)
+__device__ int g_stamp_iter;  // the limb kernel's tile loop: the iteration that stamps (hs_debug_set_stamp_iter; 0: the first)
+// (HS_STAMP_GATE: true but inside the limb kernel's step, where it names the step's stamp_on)
+#define HS_STAMP_GATE true
 #define STAMP(slot)                                                                                    \
   do {                                                                                                 \
     const unsigned r_ = blockIdx.x - g_stamp_base;                                                     \
-    if (threadIdx.x == 0 && r_ < 4096u) g_stamps[r_][slot] = __builtin_amdgcn_s_memtime();             \
+    if (threadIdx.x == 0 && r_ < 4096u && (HS_STAMP_GATE)) g_stamps[r_][slot] = __builtin_amdgcn_s_memtime(); \
   } while (0)
 #define RSTAMP(slot)                                                                                   \
   do {                                                                                                 \
@@ -3600,6 +3603,9 @@ extern "C" int hs_debug_read_stamps(unsigned long long* out, int n_rows) {
 extern "C" int hs_debug_set_stamp_base(unsigned int base) {
   return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_stamp_base), &base, sizeof(base), 0, hipMemcpyHostToDevice);
 }
+extern "C" int hs_debug_set_stamp_iter(int iter) {
+  return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_stamp_iter), &iter, sizeof(iter), 0, hipMemcpyHostToDevice);
+}
 extern "C" int hs_debug_clear_stamps() {
   static unsigned long long zero[4096][32];
   return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_stamps), zero, sizeof(zero), 0, hipMemcpyHostToDevice);
@@ -3721,7 +3727,11 @@ static int launch_limb(const hs_topo* d_topo, const hs_run_args& a, void* worksp
   launch_map m = mp;
   m.fused_w = mp.limb_rollouts ? mp.limb_waves : (a.n_rollouts + LGR - 1) / LGR;  // wavefronts per step: 8 rollouts each
   const int vsteps = mp.limb_tile ? HS_TILE_SLOTS * limb_tile_count(mp.fused_n) : mp.fused_n;
-  const dim3 grid((unsigned)((int64_t)m.fused_w * vsteps));
+  // the tile loop: a wavefront per chunk of limb_tile_loop tiles
+  // (forces mode and the fp32 build: a tile per wavefront, their instantiations have no tile loop)
+  m.limb_tile_loop = mp.limb_tile_loop < 1 || mp.tau_in || HS_REAL_IS_FLOAT ? 1 : mp.limb_tile_loop;
+  const int wsteps = mp.limb_tile ? HS_TILE_SLOTS * limb_tile_chunks(limb_tile_count(mp.fused_n), m.limb_tile_loop) : mp.fused_n;
+  const dim3 grid((unsigned)((int64_t)m.fused_w * wsteps));
   const int nm = mp.max_parts <= 18 ? 18 : (mp.max_parts <= 22 ? 22 : HS_NMAX);
   // the tile mapping's slot sequence (hs_limb_tile.h), a kernel argument: the planner's where it saves FK
   // passes (tile_plan 1; 2: its chain-aligned sequence whatever it saves), else the parity order

@@ -26,7 +26,8 @@
 // TILE (launch_map::limb_tile, hs_limb_tile.h): the same step with the wavefront turned around -- one
 // rollout x eight steps two apart -- so that the stencil's three FK rows are shared between neighbouring
 // groups through LDS (limb_tile_kd); routed by limb_tile() in hs_capi.cpp, the same outputs bitwise
-// (tests/test_gpu_limb_tile.py).
+// (tests/test_gpu_limb_tile.py). In step mode a tile-mapped wavefront runs several tiles of its rollout in turn
+// (the tile loop, launch_map::limb_tile_loop; tests/test_gpu_limb_tile_loop.py).
 
 #ifndef HS_LIMB_GROUP
 // the fused launch's block order for the limb kernel (fused_coords): groups of this many batch wavefronts
@@ -271,7 +272,7 @@ template <int NM>
 __device__ __attribute__((always_inline)) inline void limb_forces(const hs_topo* T, const hs_run_args& a,
                                                                   const hs::launch_map& mp, LimbLds<NM, true>& S, bool limb,
                                                                   int l, int L, int gbase, int nl, bool live, int b,
-                                                                  int fstep, int s_glob, const real* o,
+                                                                  int s_glob, const real* o,
                                                                   const real (&Jp)[3][3], const real (&Jz)[3][3],
                                                                   const real (&Pc)[3][3], const real* fp,
                                                                   const real (&xt)[3][3], bool bad, bool big) {
@@ -338,7 +339,7 @@ __device__ __attribute__((always_inline)) inline void limb_forces(const hs_topo*
     if (l == 0 && live) {
       atomicAdd(&g_limb_deferred, 1ull);
       const int it = atomicAdd(mp.fix_count, 1);
-      mp.fix_items[2 * it] = fstep;
+      mp.fix_items[2 * it] = s_glob - mp.fused_s0;  // the local step (formed here: not a register held up to here)
       mp.fix_items[2 * it + 1] = b;  // 2 * wavefront + half of hs_rollout_kernel's layout
     }
     return;
@@ -441,13 +442,18 @@ __device__ inline real lane_push(real v, int dst) {
 #define TDBG(slot, val, n) do {} while (0)
 #endif
 
+#ifdef HS_STAMPS
+#undef HS_STAMP_GATE
+#define HS_STAMP_GATE stamp_on  // limb_tile_kd's and limb_step's: the tile loop's chosen iteration
+#endif
 template <bool FORCES>
 __device__ __attribute__((always_inline)) inline void limb_tile_kd(
     const hs_topo* T_, real (&outer)[36][LGR * HS_LMAX], hs_link (&links)[HS_LMAX][3], const RolloutWS& W, bool straight,
     const real* u, real v, int lane, int nl, bool limb, int L, bool live, int row0, const real* tv, const real* o,
     real inv, real dt, real (&g3)[3][6], real (&Jp)[3][3], real (&Jz)[3][3], real* fp, bool& contact, bool& own,
-    real* gown, real* jvel, real (&Pc)[3][3], real* Pown, bool& bad, bool& big, int dbg_r) {
+    real* gown, real* jvel, real (&Pc)[3][3], real* Pown, bool& bad, bool& big, int dbg_r, bool stamp_on) {
   (void)dbg_r;
+  (void)stamp_on;  // (HS_STAMPS builds: this tile stamps)
   const int grp = lane >> 3, l = lane & 7;
   // which neighbour's centre row is this group's minus / plus row
   const int rprev = __shfl(row0, (lane + WAVE - LG) & (WAVE - 1)), rnext = __shfl(row0, (lane + LG) & (WAVE - 1));
@@ -653,82 +659,136 @@ __device__ __attribute__((always_inline)) inline void limb_tile_kd(
 // eight rollouts x one step
 // PLAN: none, or with TILE the launch's slot sequence (limb_tile_plan_arg, hs_limb_tile.h), read from the
 // kernel argument segment
-template <int NM, bool FORCES, bool TILE = false, class... PLAN>
-__global__ __launch_bounds__(WAVE, HS_REAL_IS_FLOAT ? HS_LIMB_WAVES_F32 : HS_LIMB_WAVES) void hs_limb_kernel(const hs_topo* __restrict__ T0, hs_run_args a,
-                                                                      RolloutWS* __restrict__ rws, hs::launch_map mp, PLAN... plan) {
-  static_assert(sizeof...(PLAN) == (TILE ? 1 : 0), "the tile mapping takes the launch's plan, the packed mapping nothing");
-  // the outer samples' pos / ust of every lane's links (kinematics), then the groups' exchange arrays:
-  // 18 KB per wavefront, 8 per CU at 2 waves / SIMD
-  // kinematics: the outer samples' pos / ust of every limb lane's links and the limbs' link records (read
-  // by every sample's FK: from LDS, not through three rounds of L1/L2 latency per sample), then the
-  // groups' exchange arrays: 17.4 KB per wavefront, 8 per CU at 2 waves / SIMD
-  __shared__ union {
+//
+// The kernel is a head and a step. The head (hs_limb_kernel) forms what belongs to the wavefront's rollouts
+// and not to a step -- the model, the rollout and its record, dt, v, the torso's direction -- and copies
+// the link records into LDS; limb_step runs one step per group from the table rows on. The packed mapping
+// runs the step once; the tile mapping runs it for each tile of the wavefront's chunk in turn (the tile
+// loop, launch_map::limb_tile_loop), so the head, all per rollout there and wave-uniform, is paid once per
+// chunk and not once per tile.
+
+// The kernel's LDS. Kinematics: the outer samples' pos / ust of every limb lane's links and the limbs' link
+// records (read by every sample's FK: from LDS, not through three rounds of L1/L2 latency per sample); then
+// the groups' exchange arrays over them: 17.4 KB per wavefront, 8 per CU at 2 waves / SIMD
+template <int NM, bool FORCES, bool LOOP>
+struct LimbShared {
+  union {
     struct {
       real outer[36][LGR * HS_LMAX];  // [Pm, Um, Pp, Up][link][component][limb lane]: one conflict-free row per value
       hs_link links[HS_LMAX][3];
     } k;
     LimbLds<NM, FORCES> g[LGR];
-  } sh;
-  LimbLds<NM, FORCES>* lds = sh.g;
-  int fstep = 0, q = (int)blockIdx.x;
-  // tile mapping: the block's virtual step is (tile, rollout of the batch wavefront's eight)
-  fused_coords<HS_LIMB_GROUP>((int)blockIdx.x, mp.fused_w, TILE ? HS_TILE_SLOTS * limb_tile_count(mp.fused_n) : mp.fused_n,
-                              fstep, q);
-  const hs_topo* __restrict__ T = mp.limb_model ? T0 + mp.limb_model[q] : T0;  // a mixed plan's wavefront model
-  {  // the link records, 8 bytes per lane and load
-    const uint64_t* src = reinterpret_cast<const uint64_t*>(&T->link[0][0]);
-    uint64_t* dst = reinterpret_cast<uint64_t*>(&sh.k.links[0][0]);
-    constexpr int NW = sizeof(sh.k.links) / sizeof(uint64_t);
-    for (int e = (int)threadIdx.x; e < NW; e += WAVE) dst[e] = src[e];
-    wave_sync();
+  };
+  __device__ hs_link (&links())[HS_LMAX][3] { return k.links; }
+};
+// The tile loop keeps the link records beside the overlay, so that a wavefront copies them once for all the
+// tiles it runs: 17.4 KB as before (the outer rows are the overlay's larger member)
+template <int NM, bool FORCES>
+struct LimbShared<NM, FORCES, true> {
+  union {
+    struct {
+      real outer[36][LGR * HS_LMAX];
+    } k;
+    LimbLds<NM, FORCES> g[LGR];
+  };
+  hs_link tl[HS_LMAX][3];
+  __device__ hs_link (&links())[HS_LMAX][3] { return tl; }
+};
+static_assert(sizeof(LimbShared<HS_NMAX, false, true>) <= 20480, "a looping wavefront's LDS: 8 per CU's 160 KB");
+
+// what hs_limb_kernel's head hands to limb_step: the lane's place, its rollout and the rollout's constants
+// (tile mapping: wave-uniform, all but the lane's place)
+struct LimbHead {
+  int lane;
+  int rslot, b;          // the group's rollout of the batch wavefront's eight, and the rollout itself
+  bool live;             // the rollout exists (tile mapping: always, its step decides per tile)
+  bool straight;
+  const RolloutWS* W;
+  real u[3];             // the torso's direction of advance
+};
+
+// The same pointer to memory this kernel only reads (the model, a rollout's record), wave-uniform, opaque to
+// the optimizer: loads through a pointer made opaque once per tile are issued in that tile instead of being
+// hoisted out of the tile loop, where their values would stay in registers across every tile. Through a
+// constant-address-space pointer: behind the previous tile's stores a global one would turn the uniform
+// reads (scalar loads, SGPRs) into vector loads.
+template <class P>
+__device__ inline const P* opaque_u(const P* p) {
+  using cptr = const __attribute__((address_space(4))) P*;
+  cptr q = (cptr)p;
+  asm volatile("" : "+s"(q));
+  return (const P*)q;
+}
+
+// a reference into the kernel argument segment, opaque to the optimizer: the fields read through it are
+// loaded where they are used (scalar loads)
+template <class P>
+__device__ inline const P& opaque_k(const P& r) {
+  using kptr = const __attribute__((address_space(4))) P*;
+  kptr q = (kptr)&r;
+  asm volatile("" : "+s"(q));
+  return *(const P*)q;
+}
+
+// One step per group. fstep: the packed mapping's local step; the tile mapping's tile, whose slot 8 tile + g
+// group g runs.
+template <int NM, bool FORCES, bool TILE, bool LOOP, class... PLAN>
+__device__ __attribute__((always_inline)) inline void limb_step(LimbShared<NM, FORCES, LOOP>& sh, const hs_topo* __restrict__ T,
+                                                                const hs_run_args& a0, const hs::launch_map& mp0,
+                                                                const LimbHead& h, int fstep, bool stamp_on,
+                                                                const PLAN&... plan) {
+  (void)stamp_on;  // (HS_STAMPS builds: this step stamps; slot 23 is the step's start, the head's end in the first)
+  STAMP(23);
+  // (tile loop: the lane's place and the model's counts are formed again in every tile, from a lane index
+  // and a model pointer made opaque here. Hoisted out of the tile loop, everything derived from them -- LDS
+  // columns, exchange lanes, request masks -- would stay in registers across all of a tile's phases)
+  int lane = h.lane;
+  if constexpr (LOOP) {
+    asm volatile("" : "+v"(lane));
+    T = opaque_u(T);
   }
-  RSTAMP(16);
-  STAMP(15);
-  const int lane = (int)threadIdx.x, grp = lane >> 3, l = lane & 7, gbase = lane & ~7;
-  const int rslot = q * LGR + (TILE ? fstep % LGR : grp);  // this group's rollout of the batch wavefront's eight
-  const int b = mp.limb_rollouts ? mp.limb_rollouts[rslot] : rslot;
-  bool live = b >= 0 && b < a.n_rollouts;
+  const int grp = lane >> 3, l = lane & 7, gbase = lane & ~7, rslot = h.rslot, b = h.b;
+  const int nl = T->n_limbs, nmj = T->nmj;
+  const bool limb = l < nl, tlane = l == LG - 1, straight = h.straight;
+  const int L = limb ? l : 0;
+  const real u[3] = {h.u[0], h.u[1], h.u[2]};
+  bool live = h.live;
   if constexpr (TILE) {
-    if (!live) return;  // the whole wavefront: one rollout
     // group g runs slot 8 tile + g's local step. An idle group (a slot past the sequence, last tile only)
     // takes the tile's first step for its indices, so every address it forms is valid, but it is neither a
     // share target nor a request: its outer rows in LDS are never written, its finite differences and all
     // that follows are computed on whatever the LDS holds (possibly NaN), and nothing of it is stored or
     // counted (every store, atomic and fix item is gated on live)
-    const int slot0 = HS_TILE_SLOTS * (fstep / LGR), ls = limb_tile_plan_step(plan..., slot0 + grp, mp.fused_n);
+    const int slot0 = HS_TILE_SLOTS * fstep, ls = limb_tile_plan_step(plan..., slot0 + grp, mp0.fused_n);
     live = ls >= 0;
-    fstep = live ? ls : limb_tile_plan_step(plan..., slot0, mp.fused_n);
+    fstep = live ? ls : limb_tile_plan_step(plan..., slot0, mp0.fused_n);
   }
-  // an idle group computes a copy of a rollout of its wavefront's model and stores nothing
-  const int bb = live || TILE ? b : (mp.limb_rollouts ? mp.limb_rollouts[q * LGR] : a.n_rollouts - 1);
-  LimbLds<NM, FORCES>& S = lds[grp];
-  const int ol = grp * HS_LMAX + (l < HS_LMAX ? l : 0);  // this limb lane's column of sh.k.outer
-  const int s_glob = mp.fused_s0 + fstep, call = s_glob / mp.fused_h;
-  const int k0 = (int)(((int64_t)a.k0 + (int64_t)call * mp.fused_h) % a.n_t) + s_glob % mp.fused_h;
-  const int row0 = k0 - mp.ktab_lo;  // table row of sample i - 2 (centre i = k0 + 2)
-  const int nl = T->n_limbs, nmj = T->nmj;
-  const bool limb = l < nl, tlane = l == LG - 1;
-  const int L = limb ? l : 0;
-  const RolloutWS& W = rws[bb];
-  const hs_gait_params& gp = a.params[bb];
-  const bool straight = (real)gp.curvature == 0 && !gp.rec_transform_flag;
+  const RolloutWS* Wp = h.W;
+  if constexpr (LOOP) Wp = opaque_u(Wp);
+  const RolloutWS& W = *Wp;
+  // (read per tile, warm scalar loads: 1 / (2 dt) is a VALU result, two VGPRs across the tile loop if the
+  // head formed it)
   const real dt = W.st.dt;
   const real v = W.st.v;
-  const NodeK n0 = load_nodek(T, 0);
-  const real u[3] = {n0.Jp(0, 0), n0.Jp(1, 0), n0.Jp(2, 0)};
+  const real inv = real(1) / (2 * dt);
+  LimbLds<NM, FORCES>& S = sh.g[grp];
+  const int ol = grp * HS_LMAX + (l < HS_LMAX ? l : 0);  // this limb lane's column of sh.k.outer
+  const int s_glob = mp0.fused_s0 + fstep, call = s_glob / mp0.fused_h;
+  const int k0 = (int)(((int64_t)a0.k0 + (int64_t)call * mp0.fused_h) % a0.n_t) + s_glob % mp0.fused_h;
+  const int row0 = k0 - mp0.ktab_lo;  // table row of sample i - 2 (centre i = k0 + 2)
   real tv[5];
 #pragma unroll
   for (int k = 0; k < 5; k += 2) tv[k] = W.t_tab[row0 + k] * v;  // gait_record's torso advance
   // the torso COM at the centre sample (particular_sub's origin o = pos(0, 0)), on every lane
   real o[3];
+  const real com0[3] = {(real)T->node[0].com[0], (real)T->node[0].com[1], (real)T->node[0].com[2]};  // load_nodek's
   if (straight) {
     for (int i = 0; i < 3; i++) o[i] = fma(tv[2], u[i], W.kf.torso[i]);
   } else {
-    mulp(load34r(W.ktor[row0 + 2] + 6), n0.com, o);
+    mulp(load34r(W.ktor[row0 + 2] + 6), com0, o);
   }
-  const real inv = real(1) / (2 * dt);
 #ifdef HS_DBG
-  const int dbg_r = live ? b * a.horizon + s_glob : -1;
+  const int dbg_r = live ? b * a0.horizon + s_glob : -1;
 #define LDBG(slot, val, n)                                                                                       \
   do {                                                                                                           \
     if (HS_DBG == (n) && dbg_r >= 0 && (size_t)dbg_r * 32 + (slot) < (1u << 22)) g_dbg[(size_t)dbg_r * 32 + (slot)] = (double)(val); \
@@ -745,7 +805,7 @@ __global__ __launch_bounds__(WAVE, HS_REAL_IS_FLOAT ? HS_LIMB_WAVES_F32 : HS_LIM
 #pragma unroll
     for (int k = 0; k < 3; k++) {
       if (straight) tb[k] = body_straight(W.kf.torso, u, tv[2 * k]);
-      else tb[k] = body_frame(load34r(W.ktor[row0 + 2 * k] + 6), n0.com);
+      else tb[k] = body_frame(load34r(W.ktor[row0 + 2 * k] + 6), com0);
     }
     part_dyn((real)T->mass[0], inv, tb[0].P, tb[1].P, tb[2].P, tb[0].U, tb[1].U, tb[2].U, g0);
     part_g(tb[1].P, o, g0);
@@ -764,8 +824,9 @@ __global__ __launch_bounds__(WAVE, HS_REAL_IS_FLOAT ? HS_LIMB_WAVES_F32 : HS_LIM
   bool bad = false, big = false;
   const hs_topo* const T_ = T;
   if constexpr (TILE) {
-    limb_tile_kd<FORCES>(T_, sh.k.outer, sh.k.links, W, straight, u, v, lane, nl, limb, L, live, row0, tv, o, inv, dt, g3,
-                         Jp, Jz, fp, contact, own, gown, jvel, Pc, Pown, bad, big, live ? b * a.horizon + s_glob : -1);
+    limb_tile_kd<FORCES>(T_, sh.k.outer, sh.links(), W, straight, u, v, lane, nl, limb, L, live, row0, tv, o, inv, dt, g3,
+                         Jp, Jz, fp, contact, own, gown, jvel, Pc, Pown, bad, big, live ? b * a0.horizon + s_glob : -1,
+                         stamp_on);
   } else if (limb) {
     const int row = row0;
     own = T->limb_own_n[L] > 0;
@@ -953,8 +1014,12 @@ __global__ __launch_bounds__(WAVE, HS_REAL_IS_FLOAT ? HS_LIMB_WAVES_F32 : HS_LIM
   wave_sync();  // S.a before the Schur system reads it
 
   STAMP(5);
+  // (tile loop: what the phases from here on read of the kernel's arguments -- the output arrays, their
+  // strides, the fixup's lists -- is read here, not held in SGPRs across the K and D phase's peak)
+  const hs_run_args& a = LOOP ? opaque_k(a0) : a0;
+  const hs::launch_map& mp = LOOP ? opaque_k(mp0) : mp0;
   if constexpr (FORCES) {
-    limb_forces<NM>(T, a, mp, S, limb, l, L, gbase, nl, live, b, fstep, s_glob, o, Jp, Jz, Pc, fp, xt, bad, big);
+    limb_forces<NM>(T, a, mp, S, limb, l, L, gbase, nl, live, b, s_glob, o, Jp, Jz, Pc, fp, xt, bad, big);
     return;
   }
   // ---- contact list in foot order (ftsolver's contact columns) ----
@@ -1213,7 +1278,7 @@ __global__ __launch_bounds__(WAVE, HS_REAL_IS_FLOAT ? HS_LIMB_WAVES_F32 : HS_LIM
     if (l == 0 && live) {
       atomicAdd(&g_limb_deferred, 1ull);  // hs_limb_stats
       const int it = atomicAdd(mp.fix_count, 1);
-      mp.fix_items[2 * it] = fstep;
+      mp.fix_items[2 * it] = s_glob - mp.fused_s0;  // the local step (formed here: not a register held up to here)
       mp.fix_items[2 * it + 1] = mp.limb_slots ? mp.limb_slots[rslot] : b;  // 2 * wavefront + half of hs_rollout_kernel's layout
     }
     return;
@@ -1282,4 +1347,93 @@ __global__ __launch_bounds__(WAVE, HS_REAL_IS_FLOAT ? HS_LIMB_WAVES_F32 : HS_LIM
   }
   STAMP(9);
   RSTAMP(17);
+}
+#undef LDBG
+#ifdef HS_STAMPS
+#undef HS_STAMP_GATE
+#define HS_STAMP_GATE true
+#endif
+
+// hs_limb_kernel's arguments of the tile mapping as the kernel argument segment holds them: in order, each
+// at its type's alignment (the code object's metadata lists the same offsets: 0, 8, 136, 144, 424)
+struct LimbTileArgs {
+  const hs_topo* T0;
+  hs_run_args a;
+  RolloutWS* rws;
+  hs::launch_map mp;
+  limb_tile_plan_arg plan;
+};
+
+template <int NM, bool FORCES, bool TILE = false, class... PLAN>
+__global__ __launch_bounds__(WAVE, HS_REAL_IS_FLOAT ? HS_LIMB_WAVES_F32 : HS_LIMB_WAVES) void hs_limb_kernel(const hs_topo* __restrict__ T0, hs_run_args a,
+                                                                      RolloutWS* __restrict__ rws, hs::launch_map mp, PLAN... plan) {
+  static_assert(sizeof...(PLAN) == (TILE ? 1 : 0), "the tile mapping takes the launch's plan, the packed mapping nothing");
+  // (LimbTileArgs above restates this parameter list for the tile loop: change both together)
+  static_assert(!TILE || (std::is_same<PLAN, limb_tile_plan_arg>::value && ...), "LimbTileArgs holds a limb_tile_plan_arg");
+  static_assert(offsetof(LimbTileArgs, a) == 8 && offsetof(LimbTileArgs, rws) == 8 + sizeof(hs_run_args) &&
+                    offsetof(LimbTileArgs, mp) == 16 + sizeof(hs_run_args) &&
+                    offsetof(LimbTileArgs, plan) == 16 + sizeof(hs_run_args) + sizeof(hs::launch_map) &&
+                    alignof(hs_run_args) == 8 && alignof(hs::launch_map) == 8,
+                "LimbTileArgs: the kernel argument segment packs the arguments in order at their alignment");
+  // The tile loop is the step mode's. Forces mode runs a tile per wavefront: with the loop around it its
+  // instantiations spill (12 to 36 bytes of scratch at 256 VGPRs, the peak is forces_solve's blocks), and
+  // launch_limb gives its launches one tile per wavefront
+  // The fp32 build (reached through HS_LIMB_TILE_MIN only) keeps a tile per wavefront too: its loop was
+  // neither measured nor tested.
+  constexpr bool LOOP = TILE && !FORCES && !HS_REAL_IS_FLOAT;
+  __shared__ LimbShared<NM, FORCES, LOOP> sh;
+  int fstep = 0, q = (int)blockIdx.x;
+  // tile mapping: the block's virtual step is (chunk of tiles, rollout of the batch wavefront's eight)
+  const int nt = TILE ? limb_tile_count(mp.fused_n) : 0, tl = LOOP ? mp.limb_tile_loop : 1;
+  fused_coords<HS_LIMB_GROUP>((int)blockIdx.x, mp.fused_w, TILE ? HS_TILE_SLOTS * limb_tile_chunks(nt, tl) : mp.fused_n, fstep,
+                              q);
+  const hs_topo* __restrict__ T = mp.limb_model ? T0 + mp.limb_model[q] : T0;  // a mixed plan's wavefront model
+  {  // the link records, 8 bytes per lane and load
+    const uint64_t* src = reinterpret_cast<const uint64_t*>(&T->link[0][0]);
+    uint64_t* dst = reinterpret_cast<uint64_t*>(&sh.links()[0][0]);
+    constexpr int NW = sizeof(hs_link[HS_LMAX][3]) / sizeof(uint64_t);
+    for (int e = (int)threadIdx.x; e < NW; e += WAVE) dst[e] = src[e];
+    wave_sync();
+  }
+  RSTAMP(16);
+  STAMP(15);
+  LimbHead h;
+  h.lane = (int)threadIdx.x;
+  h.rslot = q * LGR + (TILE ? fstep % LGR : h.lane >> 3);
+  h.b = mp.limb_rollouts ? mp.limb_rollouts[h.rslot] : h.rslot;
+  h.live = h.b >= 0 && h.b < a.n_rollouts;
+  if (TILE && !h.live) return;  // the whole wavefront: one rollout
+  // an idle group computes a copy of a rollout of its wavefront's model and stores nothing
+  const int bb = h.live ? h.b : (mp.limb_rollouts ? mp.limb_rollouts[q * LGR] : a.n_rollouts - 1);
+  h.W = &rws[bb];
+  const hs_gait_params& gp = a.params[bb];
+  h.straight = (real)gp.curvature == 0 && !gp.rec_transform_flag;
+  {
+    const NodeK n0 = load_nodek(T, 0);
+    for (int i = 0; i < 3; i++) h.u[i] = n0.Jp(i, 0);
+  }
+  if constexpr (LOOP) {
+    // the chunk's tiles in order. Between two tiles every lane meets again, whichever way it left the step
+    // (a deferred step ends its group's tile, not the wavefront), and the tile's last LDS reads (S.wd, S.a)
+    // come before the next tile's outer rows are written over them
+    // Each tile reads the kernel's arguments again, from the kernel argument segment through a pointer made
+    // opaque in the tile (scalar loads, warm after the first tile): read once at the kernel's entry they
+    // would all stay in SGPRs across the loop, ~70 on top of the head's, and spill.
+    const int c = fstep / LGR;
+    for (int t0 = limb_tile_chunk_first(c, tl), t = t0, te = limb_tile_chunk_end(c, tl, nt); t < te; t++) {
+      using kptr = const __attribute__((address_space(4))) LimbTileArgs*;
+      kptr ka = (kptr)__builtin_amdgcn_kernarg_segment_ptr();
+      asm volatile("" : "+s"(ka));
+      const LimbTileArgs& k = *(const LimbTileArgs*)ka;
+#ifdef HS_STAMPS
+      const bool stamp_on = t - t0 == g_stamp_iter;
+#else
+      const bool stamp_on = true;
+#endif
+      limb_step<NM, FORCES, true, true>(sh, T, k.a, k.mp, h, t, stamp_on, k.plan);
+      wave_sync();
+    }
+  } else {
+    limb_step<NM, FORCES, TILE, false>(sh, T, a, mp, h, TILE ? fstep / LGR : fstep, true, plan...);
+  }
 }

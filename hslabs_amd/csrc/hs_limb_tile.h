@@ -18,6 +18,8 @@
 // Every sequence holds each local step in exactly one slot, fills limb_tile_count(n) tiles, has its idle
 // slots (-1) at the end of the last tile only, and so a live slot 0 in every tile.
 //
+// The tile loop: a wavefront runs a chunk of consecutive tiles of its rollout (limb_tile_chunks).
+//
 // Plain C++ without allocation: host code, device code and the CPU tests include it.
 #pragma once
 
@@ -39,6 +41,32 @@ HS_TILE_FN int limb_tile_step(int slot, int n) {
   const int n_even = (n + 1) / 2;
   if (slot < 0 || slot >= n) return -1;
   return slot < n_even ? 2 * slot : 2 * (slot - n_even) + 1;
+}
+
+// ---- the tile loop ----
+// A wavefront runs tl consecutive tiles of its rollout, one after the other (launch_map::limb_tile_loop):
+// the launch's nt tiles are cut into chunks of tl, the last one shorter when tl does not divide nt. tl = 1
+// is a tile per wavefront (chunk c = tile c); a tl below 1 counts as 1.
+HS_TILE_FN int limb_tile_chunks(int nt, int tl) {
+  tl = tl < 1 ? 1 : tl;
+  return (nt + tl - 1) / tl;
+}
+// chunk c runs tiles [limb_tile_chunk_first, limb_tile_chunk_end) in order
+HS_TILE_FN int limb_tile_chunk_first(int c, int tl) { return c * (tl < 1 ? 1 : tl); }
+HS_TILE_FN int limb_tile_chunk_end(int c, int tl, int nt) {
+  const int e = limb_tile_chunk_first(c, tl) + (tl < 1 ? 1 : tl);
+  return e < nt ? e : nt;
+}
+
+// The routing rule's arithmetic (limb_tile_loop() in hs_capi.cpp): `tiles` tiles per wavefront, fewer while
+// the launch's chunks x rollouts stay under min_waves wavefronts in its queue, and the tiles then spread
+// evenly over the chunks that remain (5 tiles in 2 chunks: 3 + 2, not 4 + 1)
+HS_TILE_FN int limb_tile_loop_rule(int nt, int64_t n_rollouts, int tiles, int64_t min_waves) {
+  int tl = tiles < nt ? tiles : nt;
+  while (tl > 1 && (int64_t)limb_tile_chunks(nt, tl) * n_rollouts < min_waves) tl--;
+  if (tl < 1) return 1;
+  const int nc = limb_tile_chunks(nt, tl);
+  return (nt + nc - 1) / nc;
 }
 
 // ---- the plan ----

@@ -710,11 +710,17 @@ void hs_sim_free(hs_sim_t sim);
  * steps, then odd steps", which it keeps elsewhere; the outputs are the same bitwise under either.
  * HS_LIMB_TILE_PLAN=0 keeps the even/odd order everywhere, =2 takes the planner's order even where it saves
  * nothing (tests). hs_limb_tile_plan_launches: the tile-mapped launches that ran the planner's order (an
- * additive export as well). */
+ * additive export as well).
+ * A tile-mapped wavefront may run several tiles of its rollout one after the other (the tile loop), so that
+ * the rollout's share of a step is paid once per wavefront; the outputs are the same bitwise at any number.
+ * HS_LIMB_TILE_LOOP=<n> (a positive decimal number, else ignored) forces n tiles per wavefront, 1 a tile per
+ * wavefront. hs_limb_tile_loop_launches: the tile-mapped launches whose wavefronts ran more than one tile
+ * (an additive export as well). */
 int hs_model_limb_lane(hs_model_t model, int32_t* ok);
 int64_t hs_limb_launches(void);
 int64_t hs_limb_tile_launches(void);
 int64_t hs_limb_tile_plan_launches(void);
+int64_t hs_limb_tile_loop_launches(void);
 /* Diagnostics of the limb-lane kernel: its launches and the steps it deferred to the fixup launch (one,
  * two contacts, guards near their thresholds, ...) in this process; *deferred is read from the device
  * (synchronous on the current device). Either pointer may be NULL. */

@@ -3,7 +3,10 @@ the commit's hslabs_amd/csrc and include/ are extracted with `git archive` into 
 and compiled by hslabs_amd/build.py's own recipe into hslabs_amd/_build/variants/libhslabs_<name>.so
 (select it with HSLABS_VARIANT=<name>). The commit must export the current ABI (hs_run_args layout).
 
-  python tools/build_prev.py <commit> <name>
+  python tools/build_prev.py <commit> <name> [--stub-export NAME ...]
+
+--stub-export NAME: the commit lacks the additive export NAME that capi.py binds; a stub
+`int64_t NAME(void) { return 0; }` is appended to the extracted hs_capi.cpp (device code stays the commit's).
 """
 import os
 import shutil
@@ -22,6 +25,11 @@ def main():
     tar = subprocess.run(["git", "-C", ROOT, "archive", commit, "hslabs_amd/csrc", "include"], check=True,
                          capture_output=True).stdout
     subprocess.run(["tar", "-x", "-C", dst], input=tar, check=True)
+    stubs = [sys.argv[i + 1] for i, v in enumerate(sys.argv[:-1]) if v == "--stub-export"]
+    if stubs:
+        with open(os.path.join(dst, "hslabs_amd", "csrc", "hs_capi.cpp"), "a") as f:
+            for name in stubs:
+                f.write(f'\nextern "C" int64_t {name}(void) {{ return 0; }}\n')
     from hslabs_amd import build as B
     B.SRC = os.path.join(dst, "hslabs_amd", "csrc")
     out = B._compile(os.path.join(B.VARIANT_DIR, f"libhslabs_{name}.so"))

@@ -8,7 +8,10 @@ as limb_tile_kd stamps them: the one FK pass (centre rows and the first requests
 --tile --passes: instead of one window's phases, the share of the launch's tile wavefronts that take further FK
 passes, from windows over the whole launch (the planner, hs_limb_tile.h, puts the tiles of chain remainders last,
 so no single window shows it; HS_LIMB_TILE_PLAN=0 for the parity order). A wavefront counts as taking them when
-its "further FK passes" phase lasts more than half its pass 0."""
+its "further FK passes" phase lasts more than half its pass 0.
+--tile --loop TL --iter I: TL tiles per wavefront (HS_LIMB_TILE_LOOP=TL), the stamps of the wavefronts' I-th tile
+(0: the first). "tile start -> tv, o" is the step's own prelims, from the tile's start (the head's end in the
+first tile); "prelims (tv, o)" counts from the wavefront's entry, so it is the head's cost only at I = 0."""
 import ctypes
 import os
 import sys
@@ -25,15 +28,19 @@ PHASES = [("prelims (tv, o)", 15, 0), ("outer t-2dt FK", 0, 1), ("outer t+2dt FK
           ("contact blocks + Schur sums", 6, 7), ("6x6 + y", 7, 8), ("outputs", 8, 9), ("TOTAL", 15, 9)]
 
 
-TILE_PHASES = [("prelims (tv, o)", 15, 0), ("FK pass 0 (centres + requests)", 0, 1), ("further FK passes", 1, 2),
+TILE_PHASES = [("prelims (tv, o)", 15, 0), ("tile start -> tv, o", 23, 0), ("FK pass 0 (centres + requests)", 0, 1), ("further FK passes", 1, 2),
                ("exchange sync + D", 2, 3)] + PHASES[4:]
 
 
 def main():
     tile = "--tile" in sys.argv
     K = int(sys.argv[sys.argv.index("--steps") + 1]) if "--steps" in sys.argv else 20
+    tl = int(sys.argv[sys.argv.index("--loop") + 1]) if "--loop" in sys.argv else None
+    it = int(sys.argv[sys.argv.index("--iter") + 1]) if "--iter" in sys.argv else 0
     if tile:
         os.environ["HS_LIMB_TILE_MIN"] = "1"
+        if tl is not None:
+            os.environ["HS_LIMB_TILE_LOOP"] = str(tl)
     else:
         os.environ["HS_LIMB_TILE"] = "0"
     if "--build" in sys.argv or not os.path.exists(LIB):
@@ -57,14 +64,17 @@ def main():
     torch.cuda.synchronize()
     if tile and "--passes" in sys.argv:
         return passes_share(L, b, K, n)
-    L.hs_debug_set_stamp_base(ctypes.c_uint(int(os.environ.get("STEP", "4")) * (n // 8)))
+    L.hs_debug_set_stamp_base(ctypes.c_uint(int(os.environ.get("STEP", "4" if tl is None else "0")) * (n // 8)))
+    L.hs_debug_set_stamp_iter(ctypes.c_int(it))
     L.hs_debug_clear_stamps()
     b.run_calls(K, best=True)
     torch.cuda.synchronize()
     st = np.zeros((4096, 32), dtype=np.uint64)
     L.hs_debug_read_stamps(st.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong)), 4096)
     st = st.astype(np.int64)
-    st = st[(st[:, 9] != 0) & (st[:, 15] != 0)]
+    st = st[(st[:, 9] != 0) & (st[:, 15] != 0) & (st[:, 23] != 0)]
+    if tile:
+        print(f"tiles per wavefront: {tl if tl is not None else 'by the rule'}; tile {it} of each wavefront")
     for name, a, c in (TILE_PHASES if tile else PHASES):
         d = st[:, c] - st[:, a]
         print(f"{name:28s} mean {d.mean():9.0f}  p50 {np.median(d):9.0f}  p90 {np.percentile(d, 90):9.0f}  (n={len(d)})")
