@@ -414,6 +414,9 @@ step_route route(const launch_ctx& cx, const hs_run_args& a, run_entry entry) {
 #endif
 bool limb_tile(step_route rt, const hs_run_args& a, int32_t n) {
   if (rt != step_route::LIMB_FUSED || !env_switch("HS_LIMB_TILE", true)) return false;
+  // a launch the tile descriptor does not hold (longer than HS_TILE_PLAN_STEPS: only under an overridden
+  // HS_FUSED_MAX_STEPS; or table rows past 16 bits) stays packed, so the tile kernel has one path
+  if (!limb_tile_desc_ok(n, a.horizon, a.k0, a.n_t)) return false;
   if (const char* e = getenv("HS_LIMB_TILE_MIN")) {
     char* end = nullptr;
     const long min_n = strtol(e, &end, 10);
@@ -429,6 +432,9 @@ bool limb_tile(step_route rt, const hs_run_args& a, int32_t n) {
 // outputs are the same bitwise under every sequence. Measured against the parent library, B = 4096, 9
 // interleaved rounds (profiles/limb_tile_plan_ab.txt): n = 200 +4.4 %, 64 +4.2 %, forces mode +3.0 % (each
 // clear of the spread), 40 +2.4 % (not clear), the mixed plan +0.2 % (inside the spread).
+// Whichever sequence is kept, launch_limb hands it to the kernel as the tile descriptor (hs_limb_tile.h:
+// every slot's step and row, every tile's requests), measured the same way (profiles/limb_tile_desc_ab.txt):
+// n = 200 +5.5 %, 64 +4.8 %, 40 +4.5 %, the mixed plan +4.8 %, forces mode +5.3 %, each clear of the spread.
 int32_t limb_tile_plan_mode() {
   if (!env_switch("HS_LIMB_TILE_PLAN", true)) return 0;
   const char* e = getenv("HS_LIMB_TILE_PLAN");

@@ -3726,7 +3726,6 @@ static int launch_limb(const hs_topo* d_topo, const hs_run_args& a, void* worksp
   RolloutWS* ws = (RolloutWS*)workspace;
   launch_map m = mp;
   m.fused_w = mp.limb_rollouts ? mp.limb_waves : (a.n_rollouts + LGR - 1) / LGR;  // wavefronts per step: 8 rollouts each
-  const int vsteps = mp.limb_tile ? HS_TILE_SLOTS * limb_tile_count(mp.fused_n) : mp.fused_n;
   // the tile loop: a wavefront per chunk of limb_tile_loop tiles
   // (forces mode and the fp32 build: a tile per wavefront, their instantiations have no tile loop)
   m.limb_tile_loop = mp.limb_tile_loop < 1 || mp.tau_in || HS_REAL_IS_FLOAT ? 1 : mp.limb_tile_loop;
@@ -3734,27 +3733,32 @@ static int launch_limb(const hs_topo* d_topo, const hs_run_args& a, void* worksp
   const dim3 grid((unsigned)((int64_t)m.fused_w * wsteps));
   const int nm = mp.max_parts <= 18 ? 18 : (mp.max_parts <= 22 ? 22 : HS_NMAX);
   // the tile mapping's slot sequence (hs_limb_tile.h), a kernel argument: the planner's where it saves FK
-  // passes (tile_plan 1; 2: its chain-aligned sequence whatever it saves), else the parity order
-  // (n_slots = 0), as for every launch longer than a plan holds
-  limb_tile_plan_arg plan = {};
-  if (mp.limb_tile && tile_plan && mp.fused_n <= HS_TILE_PLAN_STEPS && mp.fused_h >= 1 && a.n_t >= 1 && a.k0 >= 0 &&
-      mp.fused_s0 >= 0) {
+  // passes (tile_plan 1; 2: its chain-aligned sequence whatever it saves), else the parity order. The
+  // kernel takes the sequence as its tile descriptor: every slot's step and row and every tile's requests.
+  // (A launch no descriptor holds is routed to the packed mapping by limb_tile() in hs_capi.cpp.)
+  limb_tile_desc plan = {};
+  if (mp.limb_tile) {
     const limb_tile_launch L = {mp.fused_n, mp.fused_s0, mp.fused_h, a.k0, a.n_t, mp.ktab_nl > 0 ? mp.ktab_nl : HS_LMAX};
-    bool planned = true;
+    if (!limb_tile_desc_ok(L.n, L.h, L.k0, L.n_t) || L.s0 < 0) return (int)hipErrorInvalidValue;
+    int16_t step[HS_TILE_PLAN_STEPS];
+    bool planned = false;
     if (tile_plan == 2) {
       int row[HS_TILE_PLAN_STEPS];
       limb_tile_rows(L, row);
-      limb_tile_chain_fill(row, L.n, plan.step);
+      limb_tile_chain_fill(row, L.n, step);
+      planned = true;
+    } else if (tile_plan) {
+      planned = limb_tile_plan(L, step);
     } else {
-      planned = limb_tile_plan(L, plan.step);
+      limb_tile_parity_fill(L.n, step);
     }
-    if (planned) plan.n_slots = vsteps;
+    if (!limb_tile_desc_fill(L, step, plan)) return (int)hipErrorInvalidValue;
     if (tile_planned) *tile_planned = planned;
   }
 #define HS_LIMB_LAUNCH(NM_, FORCES_)                                                                                  \
   do {                                                                                                                \
     if (mp.limb_tile)                                                                                                 \
-      hipLaunchKernelGGL((hs_limb_kernel<NM_, FORCES_, true, limb_tile_plan_arg>), grid, dim3(WAVE), 0, st, d_topo, a, ws, \
+      hipLaunchKernelGGL((hs_limb_kernel<NM_, FORCES_, true, limb_tile_desc>), grid, dim3(WAVE), 0, st, d_topo, a, ws, \
                          m, plan);                                                                                    \
     else                                                                                                              \
       hipLaunchKernelGGL((hs_limb_kernel<NM_, FORCES_, false>), grid, dim3(WAVE), 0, st, d_topo, a, ws, m);           \

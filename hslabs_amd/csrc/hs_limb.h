@@ -406,17 +406,8 @@ __device__ __attribute__((always_inline)) inline void limb_forces(const hs_topo*
 // where a value is computed, never the value. A turning gait's chain body (its pos / ust come out of
 // limb_frame with the hip frame) is pushed from the FK's lane to the reading lane (ds_permute).
 
-// the r-th set bit of a 16-bit mask (0 when there is none)
-__device__ inline int nth_bit16(uint32_t m, int r) {
-  int sel = 0, cnt = 0;
-#pragma unroll
-  for (int i = 0; i < 16; i++) {
-    const int s = (m >> i) & 1;
-    if (s && cnt == r) sel = i;
-    cnt += s;
-  }
-  return sel;
-}
+// a tile's entry of the launch's descriptor (the TILE kernels' last argument)
+__device__ inline const limb_tile_entry& limb_tile_entry_of(const limb_tile_desc& d, int tile) { return d.tile[tile]; }
 // v sent to lane dst: a lane receives what the one lane naming it sent. A lane with nothing to send names
 // lane LG - 1 (group 0's torso lane), which is no limb's lane and reads nothing it receives
 static_assert(HS_LMAX < LG, "lane LG - 1 of a group must not be a limb lane (lane_push's idle target)");
@@ -449,28 +440,19 @@ __device__ inline real lane_push(real v, int dst) {
 template <bool FORCES>
 __device__ __attribute__((always_inline)) inline void limb_tile_kd(
     const hs_topo* T_, real (&outer)[36][LGR * HS_LMAX], hs_link (&links)[HS_LMAX][3], const RolloutWS& W, bool straight,
-    const real* u, real v, int lane, int nl, bool limb, int L, bool live, int row0, const real* tv, const real* o,
-    real inv, real dt, real (&g3)[3][6], real (&Jp)[3][3], real (&Jz)[3][3], real* fp, bool& contact, bool& own,
+    const real* u, real v, int lane, int nl, bool limb, int L, bool live, int row0, uint32_t M, uint64_t req,
+    const real* tv, const real* o, real inv, real dt, real (&g3)[3][6], real (&Jp)[3][3], real (&Jz)[3][3], real* fp, bool& contact, bool& own,
     real* gown, real* jvel, real (&Pc)[3][3], real* Pown, bool& bad, bool& big, int dbg_r, bool stamp_on) {
   (void)dbg_r;
   (void)stamp_on;  // (HS_STAMPS builds: this tile stamps)
   const int grp = lane >> 3, l = lane & 7;
-  // which neighbour's centre row is this group's minus / plus row
-  const int rprev = __shfl(row0, (lane + WAVE - LG) & (WAVE - 1)), rnext = __shfl(row0, (lane + LG) & (WAVE - 1));
-  const uint64_t lv = __ballot(live);
-  const bool lprev = grp > 0 && ((lv >> ((lane - LG) & (WAVE - 1))) & 1);
-  const bool lnext = grp < LGR - 1 && ((lv >> ((lane + LG) & (WAVE - 1))) & 1);
-  const bool shm = live && lprev && rprev + 2 == row0;  // group g - 1's centre row is this group's minus row
-  const bool shp = live && lnext && rnext == row0 + 2;  // group g + 1's centre row is this group's plus row
-  // the requests: bit 2 g group g's minus row, bit 2 g + 1 its plus row, served in bit order
-  uint32_t M = 0;
-  {
-    const uint64_t bm = __ballot(live && !shm), bp = __ballot(live && !shp);
-#pragma unroll
-    for (int g = 0; g < LGR; g++)
-      M |= (uint32_t)((bm >> (LG * g)) & 1) << (2 * g) | (uint32_t)((bp >> (LG * g)) & 1) << (2 * g + 1);
-  }
+  // The tile's requests, from its descriptor (wave-uniform): M's bit 2 g is group g's minus row, bit 2 g + 1
+  // its plus row, served in bit order; req lists them in that order, 4 bits each. A live group's row that is
+  // no request is its neighbour's centre row.
+  const bool shm = live && !((M >> (2 * grp)) & 1);      // group g - 1's centre row is this group's minus row
+  const bool shp = live && !((M >> (2 * grp + 1)) & 1);  // group g + 1's centre row is this group's plus row
   const int nreq = __popc(M);
+  auto nth_req = [req](int r) { return (int)(req >> (4 * r)) & 15; };  // the r-th request's bit of M (r < 16)
   const int nidle = LG - nl;             // lanes of a group the step leaves idle in this phase
   const int E0 = (LGR * nidle) / nl;     // requests the first pass takes on them
   // the pass that serves this group's minus / plus row (a turning gait's chain body arrives with it)
@@ -491,7 +473,7 @@ __device__ __attribute__((always_inline)) inline void limb_tile_kd(
       extra = rq < E0 && rq < nreq;
       if (!extra) rq = 0, fL = 0;
     }
-    const int bit = nth_bit16(M, rq), gr = bit >> 1, side = bit & 1;
+    const int bit = nth_req(rq), gr = bit >> 1, side = bit & 1;
     const int rr = __shfl(row0, gr * LG);
     const int frow = limb ? row0 + 2 : rr + 4 * side;
     const int dst = gr * LG + fL;
@@ -550,7 +532,7 @@ __device__ __attribute__((always_inline)) inline void limb_tile_kd(
   // ---- further passes: eight requests each, request base + g on group g's limb lanes ----
   for (int base = E0, pass = 1; base < nreq; base += LGR, pass++) {
     const bool act = limb && base + grp < nreq;
-    const int bit = nth_bit16(M, act ? base + grp : 0), gr = bit >> 1, side = bit & 1;
+    const int bit = nth_req(act ? base + grp : 0), gr = bit >> 1, side = bit & 1;
     const int frow = __shfl(row0, gr * LG) + 4 * side;
     const int dst = act ? gr * LG + L : -1;
     BodyS ob;
@@ -657,8 +639,8 @@ __device__ __attribute__((always_inline)) inline void limb_tile_kd(
 // every lane of the group; a B_f near singular defers the step to the forces fixup launch)
 // TILE: the tile mapping (a wavefront = one rollout x eight steps, limb_tile_kd above); else a wavefront =
 // eight rollouts x one step
-// PLAN: none, or with TILE the launch's slot sequence (limb_tile_plan_arg, hs_limb_tile.h), read from the
-// kernel argument segment
+// PLAN: none, or with TILE the launch's tile descriptor (limb_tile_desc, hs_limb_tile.h: the slot sequence with
+// every slot's row and every tile's requests), read from the kernel argument segment
 //
 // The kernel is a head and a step. The head (hs_limb_kernel) forms what belongs to the wavefront's rollouts
 // and not to a step -- the model, the rollout and its record, dt, v, the torso's direction -- and copies
@@ -753,15 +735,24 @@ __device__ __attribute__((always_inline)) inline void limb_step(LimbShared<NM, F
   const int L = limb ? l : 0;
   const real u[3] = {h.u[0], h.u[1], h.u[2]};
   bool live = h.live;
+  int tile_row = 0;       // tile mapping: the group's row as limb_tile_row forms it,
+  uint32_t tile_M = 0;    // the tile's request mask
+  uint64_t tile_req = 0;  // and its requests in service order (limb_tile_entry)
   if constexpr (TILE) {
     // group g runs slot 8 tile + g's local step. An idle group (a slot past the sequence, last tile only)
     // takes the tile's first step for its indices, so every address it forms is valid, but it is neither a
     // share target nor a request: its outer rows in LDS are never written, its finite differences and all
     // that follows are computed on whatever the LDS holds (possibly NaN), and nothing of it is stored or
     // counted (every store, atomic and fix item is gated on live)
-    const int slot0 = HS_TILE_SLOTS * fstep, ls = limb_tile_plan_step(plan..., slot0 + grp, mp0.fused_n);
-    live = ls >= 0;
-    fstep = live ? ls : limb_tile_plan_step(plan..., slot0, mp0.fused_n);
+    // The step and its table row come from the launch's tile descriptor (hs_limb_tile.h), the same for
+    // every rollout: one load per lane from the kernel argument segment, no row arithmetic here.
+    const limb_tile_entry& te = limb_tile_entry_of(plan..., fstep);
+    const limb_tile_slot sl = te.slot[(unsigned)grp];
+    live = sl.step >= 0;
+    fstep = live ? sl.step : te.slot[0].step;
+    tile_row = sl.row;
+    tile_M = te.M;
+    tile_req = te.req;
   }
   const RolloutWS* Wp = h.W;
   if constexpr (LOOP) Wp = opaque_u(Wp);
@@ -773,8 +764,14 @@ __device__ __attribute__((always_inline)) inline void limb_step(LimbShared<NM, F
   const real inv = real(1) / (2 * dt);
   LimbLds<NM, FORCES>& S = sh.g[grp];
   const int ol = grp * HS_LMAX + (l < HS_LMAX ? l : 0);  // this limb lane's column of sh.k.outer
-  const int s_glob = mp0.fused_s0 + fstep, call = s_glob / mp0.fused_h;
-  const int k0 = (int)(((int64_t)a0.k0 + (int64_t)call * mp0.fused_h) % a0.n_t) + s_glob % mp0.fused_h;
+  const int s_glob = mp0.fused_s0 + fstep;
+  int k0;
+  if constexpr (TILE) {
+    k0 = tile_row;
+  } else {
+    const int call = s_glob / mp0.fused_h;
+    k0 = (int)(((int64_t)a0.k0 + (int64_t)call * mp0.fused_h) % a0.n_t) + s_glob % mp0.fused_h;
+  }
   const int row0 = k0 - mp0.ktab_lo;  // table row of sample i - 2 (centre i = k0 + 2)
   real tv[5];
 #pragma unroll
@@ -824,9 +821,9 @@ __device__ __attribute__((always_inline)) inline void limb_step(LimbShared<NM, F
   bool bad = false, big = false;
   const hs_topo* const T_ = T;
   if constexpr (TILE) {
-    limb_tile_kd<FORCES>(T_, sh.k.outer, sh.links(), W, straight, u, v, lane, nl, limb, L, live, row0, tv, o, inv, dt, g3,
-                         Jp, Jz, fp, contact, own, gown, jvel, Pc, Pown, bad, big, live ? b * a0.horizon + s_glob : -1,
-                         stamp_on);
+    limb_tile_kd<FORCES>(T_, sh.k.outer, sh.links(), W, straight, u, v, lane, nl, limb, L, live, row0, tile_M, tile_req, tv,
+                         o, inv, dt, g3, Jp, Jz, fp, contact, own, gown, jvel, Pc, Pown, bad, big,
+                         live ? b * a0.horizon + s_glob : -1, stamp_on);
   } else if (limb) {
     const int row = row0;
     own = T->limb_own_n[L] > 0;
@@ -1361,15 +1358,15 @@ struct LimbTileArgs {
   hs_run_args a;
   RolloutWS* rws;
   hs::launch_map mp;
-  limb_tile_plan_arg plan;
+  limb_tile_desc plan;
 };
 
 template <int NM, bool FORCES, bool TILE = false, class... PLAN>
 __global__ __launch_bounds__(WAVE, HS_REAL_IS_FLOAT ? HS_LIMB_WAVES_F32 : HS_LIMB_WAVES) void hs_limb_kernel(const hs_topo* __restrict__ T0, hs_run_args a,
                                                                       RolloutWS* __restrict__ rws, hs::launch_map mp, PLAN... plan) {
-  static_assert(sizeof...(PLAN) == (TILE ? 1 : 0), "the tile mapping takes the launch's plan, the packed mapping nothing");
+  static_assert(sizeof...(PLAN) == (TILE ? 1 : 0), "the tile mapping takes the launch's tile descriptor, the packed mapping nothing");
   // (LimbTileArgs above restates this parameter list for the tile loop: change both together)
-  static_assert(!TILE || (std::is_same<PLAN, limb_tile_plan_arg>::value && ...), "LimbTileArgs holds a limb_tile_plan_arg");
+  static_assert(!TILE || (std::is_same<PLAN, limb_tile_desc>::value && ...), "LimbTileArgs holds a limb_tile_desc");
   static_assert(offsetof(LimbTileArgs, a) == 8 && offsetof(LimbTileArgs, rws) == 8 + sizeof(hs_run_args) &&
                     offsetof(LimbTileArgs, mp) == 16 + sizeof(hs_run_args) &&
                     offsetof(LimbTileArgs, plan) == 16 + sizeof(hs_run_args) + sizeof(hs::launch_map) &&

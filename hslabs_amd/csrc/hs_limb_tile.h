@@ -3,9 +3,10 @@
 // Tile t of a rollout is slots 8 t .. 8 t + 7 of the launch's slot sequence, one slot per 8-lane group of
 // the wavefront; slots past the sequence are idle groups (in the last tile only). A group's stencil rows
 // t - 2dt and t + 2dt are its neighbours' centre rows wherever consecutive slots hold steps whose table
-// rows are 2 apart (the kernel tests the rows themselves, not the sequence, so any sequence gives the same
+// rows are 2 apart (decided from the rows themselves, not the sequence, so any sequence gives the same
 // values). Every row no neighbour holds is a request (limb_tile_kd); the first E0 of a tile run beside the
-// centre rows, every further eight cost the wavefront one more FK pass.
+// centre rows, every further eight cost the wavefront one more FK pass. The host decides all this once per
+// launch and hands it to the kernel as the tile descriptor (limb_tile_desc).
 //
 // Two sequences:
 //   the parity order (limb_tile_step): all even local steps ascending, then all odd ones. Consecutive
@@ -72,8 +73,9 @@ HS_TILE_FN int limb_tile_loop_rule(int nt, int64_t n_rollouts, int tiles, int64_
 // ---- the plan ----
 constexpr int HS_TILE_PLAN_STEPS = 256;  // the longest launch a plan holds (HS_FUSED_MAX_STEPS' default)
 
-// The planned slot sequence as the TILE kernels take it (a by-value kernel argument): n_slots =
-// 8 * limb_tile_count(n) when step[] holds a plan, 0 for the parity order.
+// A slot sequence with the parity order as its default (the TILE kernels' argument before the tile
+// descriptor below; the planner's tests still read sequences through it): n_slots = 8 * limb_tile_count(n)
+// when step[] holds a plan, 0 for the parity order.
 struct limb_tile_plan_arg {
   int32_t n_slots;
   int16_t step[HS_TILE_PLAN_STEPS];
@@ -221,4 +223,76 @@ HS_TILE_FN bool limb_tile_plan(const limb_tile_launch& L, int16_t* step, int* pa
   if (pc < pp) return true;
   for (int s = 0; s < HS_TILE_SLOTS * limb_tile_count(L.n); s++) step[s] = par[s];
   return false;
+}
+
+// ---- the tile descriptor ----
+// What the TILE kernels take of a launch's slot sequence (a by-value kernel argument, built by launch_limb
+// from the sequence kept: the planner's or the parity order): per tile, every slot's local step and table
+// row, and the tile's requests. All of it is the same for every rollout of the launch, so the host forms it
+// once and the kernel reads it (limb_step, limb_tile_kd) instead of deriving it per lane and tile. What
+// depends on the wavefront's model stays in the kernel: E0 and with it the pass of a request.
+constexpr int HS_TILE_DESC_TILES = HS_TILE_PLAN_STEPS / HS_TILE_SLOTS;  // 32
+
+struct alignas(4) limb_tile_slot {
+  int16_t step;  // the slot's local step, -1 for an idle slot
+  int16_t row;   // limb_tile_row of that step; an idle slot holds the row of the tile's slot 0
+};
+struct limb_tile_entry {
+  limb_tile_slot slot[HS_TILE_SLOTS];
+  uint32_t M;     // the requests: bit 2 g slot g's minus row, bit 2 g + 1 its plus row (limb_tile_requests' rule)
+  uint32_t nreq;  // their number
+  uint64_t req;   // the requests in service order (ascending bit of M), 4 bits each: request r is (req >> 4 r) & 15
+};
+struct limb_tile_desc {
+  int32_t n_tiles;  // limb_tile_count(n)
+  int32_t pad_;
+  limb_tile_entry tile[HS_TILE_DESC_TILES];
+};
+static_assert(sizeof(limb_tile_entry) == 48, "a tile's descriptor: 8 slots of 4 bytes, M, nreq and the request list");
+static_assert(sizeof(limb_tile_desc) == 8 + 48 * HS_TILE_DESC_TILES && sizeof(limb_tile_desc) <= 1600,
+              "the descriptor travels by value: with the kernel's other arguments well under 4 KB");
+
+// whether a descriptor holds the launch: a plan's length, and rows that fit 16 bits
+HS_TILE_FN bool limb_tile_desc_ok(int n, int h, int k0, int n_t) {
+  return n >= 1 && n <= HS_TILE_PLAN_STEPS && h >= 1 && n_t >= 1 && k0 >= 0 && (int64_t)n_t + h <= 32767;
+}
+
+// one tile's entry from its eight slots (step[g], -1 idle) and the launch's steps' rows
+HS_TILE_FN void limb_tile_entry_fill(const int* row, const int16_t* slots, limb_tile_entry& e) {
+  const int first = slots[0] >= 0 ? row[slots[0]] : 0;
+  uint32_t M = 0;
+  for (int g = 0; g < HS_TILE_SLOTS; g++) {
+    e.slot[g].step = (int16_t)(slots[g] >= 0 ? slots[g] : -1);
+    e.slot[g].row = (int16_t)(slots[g] >= 0 ? row[slots[g]] : first);
+    if (slots[g] < 0) continue;
+    const int r = row[slots[g]];
+    const bool shm = g > 0 && slots[g - 1] >= 0 && row[slots[g - 1]] + 2 == r;
+    const bool shp = g < HS_TILE_SLOTS - 1 && slots[g + 1] >= 0 && row[slots[g + 1]] == r + 2;
+    M |= (uint32_t)!shm << (2 * g) | (uint32_t)!shp << (2 * g + 1);
+  }
+  e.M = M;
+  e.nreq = 0;
+  e.req = 0;
+  for (int bit = 0; bit < 2 * HS_TILE_SLOTS; bit++)
+    if ((M >> bit) & 1) e.req |= (uint64_t)bit << (4 * e.nreq++);
+}
+
+// the descriptor of a launch's sequence step[8 * limb_tile_count(L.n)] (limb_tile_plan's, limb_tile_chain_fill's
+// or limb_tile_parity_fill's). False, and d untouched, where limb_tile_desc_ok says no.
+HS_TILE_FN bool limb_tile_desc_fill(const limb_tile_launch& L, const int16_t* step, limb_tile_desc& d) {
+  if (!limb_tile_desc_ok(L.n, L.h, L.k0, L.n_t) || L.s0 < 0) return false;
+  int row[HS_TILE_PLAN_STEPS];
+  for (int i = 0; i < L.n; i++) row[i] = limb_tile_row(L, i);
+  d.n_tiles = limb_tile_count(L.n);
+  d.pad_ = 0;
+  for (int t = 0; t < HS_TILE_DESC_TILES; t++) {
+    if (t < d.n_tiles) {
+      limb_tile_entry_fill(row, step + HS_TILE_SLOTS * t, d.tile[t]);
+    } else {
+      for (int g = 0; g < HS_TILE_SLOTS; g++) d.tile[t].slot[g].step = -1, d.tile[t].slot[g].row = 0;
+      d.tile[t].M = d.tile[t].nreq = 0;
+      d.tile[t].req = 0;
+    }
+  }
+  return true;
 }
