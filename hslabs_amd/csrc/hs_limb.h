@@ -187,14 +187,14 @@ __device__ inline BodyS body_frame(const A34& A, const real* com) {
 }
 
 // Limb L's hip joint frame J at one sample and its chain body's pos / ust (limb_own_n <= 1, hs_topo::
-// limb_lane_ok): straight gaits from KinFrames at tv, turning ones from the torso record's frame and the
-// chain products (kin_sample_tab)
+// limb_lane_ok): straight gaits from KinFrames at tv (kf: the rollout's, W.kf or the tile loop's copy of it
+// in LDS), turning ones from the torso record's frame and the chain products (kin_sample_tab)
 __device__ __attribute__((always_inline)) inline A34 limb_frame(const hs_topo* T, int L, bool straight, const bool own,
-                                                                const RolloutWS& W, int row, const real* u, real tv,
-                                                                BodyS& ob) {
+                                                                const RolloutWS& W, const KinFrames& kf, int row,
+                                                                const real* u, real tv, BodyS& ob) {
   if (straight) {
-    if (own) ob = body_straight(W.kf.own[L][0], u, tv);
-    return frame_at(load34r(W.kf.J0[L]), u, tv);
+    if (own) ob = body_straight(kf.own[L][0], u, tv);
+    return frame_at(load34r(kf.J0[L]), u, tv);
   }
   A34 A = load34r(W.ktor[row] + 6);
   const int clen = T->limb_chain_len[L];
@@ -392,6 +392,72 @@ __device__ __attribute__((always_inline)) inline void limb_forces(const hs_topo*
 }
 #undef FDBG
 
+// The tile loop's wavefront constants. What a tile reads of the model per limb lane and of the rollout's
+// record is the same in every tile of the chunk, and read from global memory it is a chain of dependent
+// round trips per tile (limb_node -> mass, the slot -> t_tab -> the frames) that only the SIMD's one other
+// wave can cover. The head stages it in LDS once per wavefront, beside the link records.
+// A limb lane's model constants (entry l: limb l; for l < nkids also the root's kid l)
+struct LimbLaneK {
+  real m[3], mown;  // masses of the limb's three links and of the chain body it owns
+  uint32_t nodes;   // the links' nodes, a byte each (top first), the owned chain body's node in byte 3
+  uint32_t hf;      // the links' hinges, a byte each, the foot index in byte 3
+  uint32_t kid;     // byte 0: the root's kid l, byte 1: its subtree size, byte 2: the limb owns a chain body
+  uint32_t pad_;
+};
+static_assert(HS_NMAX < 256 && HS_LMAX < 256, "LimbLaneK packs node, hinge and foot indices into bytes");
+// the rollout's sample times and straight-gait frames as RolloutWS holds them (one contiguous copy)
+struct LimbRolloutK {
+  real t_tab[HS_KTAB];
+  KinFrames kf;
+};
+static_assert(offsetof(RolloutWS, kf) == offsetof(RolloutWS, t_tab) + sizeof(real[HS_KTAB]) &&
+                  offsetof(LimbRolloutK, kf) == sizeof(real[HS_KTAB]),
+              "LimbRolloutK mirrors RolloutWS from t_tab through kf");
+
+// What limb_step and limb_tile_kd read of the model per limb lane: from the topology (the packed mapping,
+// forces mode, the fp32 build), or from the wavefront's LimbLaneK block in LDS (the tile loop)
+template <bool LOOP>
+struct LimbModelK {
+  const hs_topo* T;
+  const LimbLaneK* k;
+  __device__ bool own(int L) const {
+    if constexpr (LOOP) return (k[L].kid >> 16) & 1;
+    else return T->limb_own_n[L] > 0;
+  }
+  __device__ int node(int L, int kk) const {
+    if constexpr (LOOP) return (k[L].nodes >> (8 * kk)) & 255;
+    else return T->limb_node[L][kk];
+  }
+  __device__ int own_node(int L) const {
+    if constexpr (LOOP) return k[L].nodes >> 24;
+    else return T->limb_own[L][0];
+  }
+  __device__ real mass(int L, int kk) const {
+    if constexpr (LOOP) return k[L].m[kk];
+    else return (real)T->mass[T->limb_node[L][kk]];
+  }
+  __device__ real mass_own(int L) const {
+    if constexpr (LOOP) return k[L].mown;
+    else return (real)T->mass[T->limb_own[L][0]];
+  }
+  __device__ int hinge(int L, int kk) const {
+    if constexpr (LOOP) return (k[L].hf >> (8 * kk)) & 255;
+    else return T->link[L][kk].hinge;
+  }
+  __device__ int foot(int L) const {
+    if constexpr (LOOP) return k[L].hf >> 24;
+    else return T->link[L][2].foot;
+  }
+  __device__ int kid(int l) const {
+    if constexpr (LOOP) return k[l].kid & 255;
+    else return T->node[0].kids[l];
+  }
+  __device__ int kid_size(int l, int c) const {
+    if constexpr (LOOP) return (k[l].kid >> 8) & 255;
+    else return T->node[c].size;
+  }
+};
+
 // ---- the tile mapping's K and D phase ----
 // A tile-mapped wavefront is one rollout x eight steps: group g runs the local step of slot 8 tile + g of the
 // launch's sequence (hs_limb_tile.h), two rows after group g - 1's wherever the sequence has no break, so
@@ -437,9 +503,12 @@ __device__ inline real lane_push(real v, int dst) {
 #undef HS_STAMP_GATE
 #define HS_STAMP_GATE stamp_on  // limb_tile_kd's and limb_step's: the tile loop's chosen iteration
 #endif
-template <bool FORCES>
+// mk, kf, ttab: the model's per-lane constants, the rollout's straight-gait frames and its sample times, from
+// global memory or (LOOP) from the wavefront's copies in LDS
+template <bool FORCES, bool LOOP>
 __device__ __attribute__((always_inline)) inline void limb_tile_kd(
-    const hs_topo* T_, real (&outer)[36][LGR * HS_LMAX], hs_link (&links)[HS_LMAX][3], const RolloutWS& W, bool straight,
+    const hs_topo* T_, const LimbModelK<LOOP>& mk, const KinFrames& kf, const real* ttab,
+    real (&outer)[36][LGR * HS_LMAX], hs_link (&links)[HS_LMAX][3], const RolloutWS& W, bool straight,
     const real* u, real v, int lane, int nl, bool limb, int L, bool live, int row0, uint32_t M, uint64_t req,
     const real* tv, const real* o, real inv, real dt, real (&g3)[3][6], real (&Jp)[3][3], real (&Jz)[3][3], real* fp, bool& contact, bool& own,
     real* gown, real* jvel, real (&Pc)[3][3], real* Pown, bool& bad, bool& big, int dbg_r, bool stamp_on) {
@@ -461,7 +530,7 @@ __device__ __attribute__((always_inline)) inline void limb_tile_kd(
   auto col = [](int ln) { return (ln >> 3) * HS_LMAX + (ln & 7); };  // a limb lane's column of sh.k.outer
   real P[3][3], U[3][3];  // a limb lane's links at its centre row
   BodyS om, op, oc;       // its chain body at the three rows
-  own = limb && T_->limb_own_n[L] > 0;
+  own = limb && mk.own(L);
   // ---- pass 0: the centre rows on the limb lanes, the first requests on the idle lanes ----
   {
     int rq = 0, fL = L;
@@ -485,8 +554,10 @@ __device__ __attribute__((always_inline)) inline void limb_tile_kd(
     for (int j = 0; j < 3; j++) ob.P[j] = ob.U[j] = real(0);
     if (limb || extra) {
       const hs_topo* T = opaque_s(T_);
-      const bool fown = T->limb_own_n[fL] > 0;
-      const A34 J = limb_frame(T, fL, straight, fown, W, frow, u, W.t_tab[frow] * v, ob);
+      const bool fown = LimbModelK<LOOP>{T, mk.k}.own(fL);
+      // (tile loop: a limb lane's row is its centre row, whose time it holds; only a request looks one up)
+      const real tvf = LOOP && limb ? tv[2] : ttab[frow] * v;
+      const A34 J = limb_frame(T, fL, straight, fown, W, kf, frow, u, tvf, ob);
       const real* ja = W.ktab[frow][fL];
       real sq[3], cq[3];
 #pragma unroll
@@ -543,8 +614,8 @@ __device__ __attribute__((always_inline)) inline void limb_tile_kd(
       real P2[3][3], U2[3][3];
       bool nb = false;
       const hs_topo* T = opaque_s(T_);
-      limb_outer(T, links[L], limb_frame(T, L, straight, own, W, frow, u, W.t_tab[frow] * v, ob), W.ktab[frow][L], P2, U2,
-                 nb);
+      limb_outer(T, links[L], limb_frame(T, L, straight, own, W, kf, frow, u, ttab[frow] * v, ob), W.ktab[frow][L], P2,
+                 U2, nb);
       const int c = col(dst), o0 = side ? 18 : 0;
 #pragma unroll
       for (int kk = 0; kk < 3; kk++)
@@ -569,12 +640,13 @@ __device__ __attribute__((always_inline)) inline void limb_tile_kd(
   wave_sync();  // every group's outer rows
   if (limb) {
     const hs_topo* T = T_;
+    (void)T;  // (HS_DBG builds: the parts' rows)
     if (own) {
       if (straight) {  // kin_sample_straight's features: limb_frame's own expressions at the outer rows
-        om = body_straight(W.kf.own[L][0], u, tv[0]);
-        op = body_straight(W.kf.own[L][0], u, tv[4]);
+        om = body_straight(kf.own[L][0], u, tv[0]);
+        op = body_straight(kf.own[L][0], u, tv[4]);
       }
-      part_dyn((real)T->mass[T->limb_own[L][0]], inv, om.P, oc.P, op.P, om.U, oc.U, op.U, gown);
+      part_dyn(mk.mass_own(L), inv, om.P, oc.P, op.P, om.U, oc.U, op.U, gown);
       part_g(oc.P, o, gown);
       if constexpr (FORCES)
         for (int j = 0; j < 3; j++) Pown[j] = oc.P[j];
@@ -599,7 +671,7 @@ __device__ __attribute__((always_inline)) inline void limb_tile_kd(
         Pp[j] = outer[18 + 3 * kk + j][ol];
         Up[j] = outer[27 + 3 * kk + j][ol];
       }
-      part_dyn((real)T->mass[T->limb_node[L][kk]], inv, Pm, P0, Pp, Um, U0, Up, g3[kk]);
+      part_dyn(mk.mass(L, kk), inv, Pm, P0, Pp, Um, U0, Up, g3[kk]);
       TDBG(T->limb_node[L][kk], P0[0], 1);
       TDBG(T->limb_node[L][kk], U0[0], 5);
       TDBG(T->limb_node[L][kk], g3[kk][0], 2);
@@ -616,6 +688,27 @@ __device__ __attribute__((always_inline)) inline void limb_tile_kd(
       TDBG(T->limb_node[L][kk], g3[kk][3], 3);
     }
     bad = W.kbad[row0 + 2][L] != 0;
+    if constexpr (LOOP) {
+      // the range test's nine joint values and the joint rates' six in one batch of loads (the limb's five
+      // rows), the +-pi wrap as selects between the same doubles the branches below form: loaded pair by
+      // pair behind each joint's wrap they were three more round trips per tile
+      real jq[5][3];
+#pragma unroll
+      for (int r = 0; r < 5; r++)
+#pragma unroll
+        for (int kk = 0; kk < 3; kk++) jq[r][kk] = W.ktab[row0 + r][L][kk];
+#pragma unroll
+      for (int r = 0; r < 5; r += 2)
+#pragma unroll
+        for (int kk = 0; kk < 3; kk++) big |= sincos_big(jq[r][kk]);
+#pragma unroll
+      for (int kk = 0; kk < 3; kk++) {
+        const real dd = jq[3][kk] - jq[1][kk];
+        const real lo = dd - 2 * kPi, hi = dd + 2 * kPi;
+        jvel[kk] = (dd > kPi ? lo : (dd < -kPi ? hi : dd)) / (2 * dt);
+      }
+      return;
+    }
     // a joint value past sincos_k_small's range at any of the three rows defers the step
 #pragma unroll
     for (int r = 0; r < 5; r += 2)
@@ -647,7 +740,8 @@ __device__ __attribute__((always_inline)) inline void limb_tile_kd(
 // the link records into LDS; limb_step runs one step per group from the table rows on. The packed mapping
 // runs the step once; the tile mapping runs it for each tile of the wavefront's chunk in turn (the tile
 // loop, launch_map::limb_tile_loop), so the head, all per rollout there and wave-uniform, is paid once per
-// chunk and not once per tile.
+// chunk and not once per tile. The tile loop's head also stages the wavefront's constants in LDS (LimbLaneK,
+// LimbRolloutK above), so that a tile reads them without a round trip to global memory.
 
 // The kernel's LDS. Kinematics: the outer samples' pos / ust of every limb lane's links and the limbs' link
 // records (read by every sample's FK: from LDS, not through three rounds of L1/L2 latency per sample); then
@@ -664,7 +758,8 @@ struct LimbShared {
   __device__ hs_link (&links())[HS_LMAX][3] { return k.links; }
 };
 // The tile loop keeps the link records beside the overlay, so that a wavefront copies them once for all the
-// tiles it runs: 17.4 KB as before (the outer rows are the overlay's larger member)
+// tiles it runs, and the wavefront constants after them: 17,856 + 2,384 B, under the 20,480 B that leave 8
+// one-wavefront workgroups per CU (160 KiB / 8)
 template <int NM, bool FORCES>
 struct LimbShared<NM, FORCES, true> {
   union {
@@ -674,6 +769,8 @@ struct LimbShared<NM, FORCES, true> {
     LimbLds<NM, FORCES> g[LGR];
   };
   hs_link tl[HS_LMAX][3];
+  LimbRolloutK rk;
+  LimbLaneK lk[LG];
   __device__ hs_link (&links())[HS_LMAX][3] { return tl; }
 };
 static_assert(sizeof(LimbShared<HS_NMAX, false, true>) <= 20480, "a looping wavefront's LDS: 8 per CU's 160 KB");
@@ -747,9 +844,26 @@ __device__ __attribute__((always_inline)) inline void limb_step(LimbShared<NM, F
     // The step and its table row come from the launch's tile descriptor (hs_limb_tile.h), the same for
     // every rollout: one load per lane from the kernel argument segment, no row arithmetic here.
     const limb_tile_entry& te = limb_tile_entry_of(plan..., fstep);
-    const limb_tile_slot sl = te.slot[(unsigned)grp];
+    limb_tile_slot sl;
+    int first;
+    if constexpr (LOOP) {
+      // the tile's eight slots by one scalar load beside M and req, the group's selected from them: a load
+      // per lane would be a round trip at the head of every tile, ahead of everything that hangs on the row
+      static_assert(sizeof(limb_tile_slot) == 4 && HS_TILE_SLOTS == 8, "a slot is one word: step low, row high");
+      uint32_t w[HS_TILE_SLOTS];
+      __builtin_memcpy(w, te.slot, sizeof(w));
+      uint32_t ws = w[0];
+#pragma unroll
+      for (int g = 1; g < HS_TILE_SLOTS; g++) ws = grp == g ? w[g] : ws;
+      sl.step = (int16_t)(ws & 0xFFFFu);
+      sl.row = (int16_t)(ws >> 16);
+      first = (int16_t)(w[0] & 0xFFFFu);
+    } else {
+      sl = te.slot[(unsigned)grp];
+      first = te.slot[0].step;
+    }
     live = sl.step >= 0;
-    fstep = live ? sl.step : te.slot[0].step;
+    fstep = live ? sl.step : first;
     tile_row = sl.row;
     tile_M = te.M;
     tile_req = te.req;
@@ -773,9 +887,22 @@ __device__ __attribute__((always_inline)) inline void limb_step(LimbShared<NM, F
     k0 = (int)(((int64_t)a0.k0 + (int64_t)call * mp0.fused_h) % a0.n_t) + s_glob % mp0.fused_h;
   }
   const int row0 = k0 - mp0.ktab_lo;  // table row of sample i - 2 (centre i = k0 + 2)
+  // the model's per-lane constants, the rollout's sample times and straight-gait frames: the tile loop's
+  // copies in LDS (the head's), else global memory
+  const real* ttab;
+  const KinFrames* kfp;
+  LimbModelK<LOOP> mk{T, nullptr};
+  if constexpr (LOOP) {
+    ttab = sh.rk.t_tab;
+    kfp = &sh.rk.kf;
+    mk.k = sh.lk;
+  } else {
+    ttab = W.t_tab;
+    kfp = &W.kf;
+  }
   real tv[5];
 #pragma unroll
-  for (int k = 0; k < 5; k += 2) tv[k] = W.t_tab[row0 + k] * v;  // gait_record's torso advance
+  for (int k = 0; k < 5; k += 2) tv[k] = ttab[row0 + k] * v;  // gait_record's torso advance
   // the torso COM at the centre sample (particular_sub's origin o = pos(0, 0)), on every lane
   real o[3];
   const real com0[3] = {(real)T->node[0].com[0], (real)T->node[0].com[1], (real)T->node[0].com[2]};  // load_nodek's
@@ -821,7 +948,7 @@ __device__ __attribute__((always_inline)) inline void limb_step(LimbShared<NM, F
   bool bad = false, big = false;
   const hs_topo* const T_ = T;
   if constexpr (TILE) {
-    limb_tile_kd<FORCES>(T_, sh.k.outer, sh.links(), W, straight, u, v, lane, nl, limb, L, live, row0, tile_M, tile_req, tv,
+    limb_tile_kd<FORCES, LOOP>(T_, mk, *kfp, ttab, sh.k.outer, sh.links(), W, straight, u, v, lane, nl, limb, L, live, row0, tile_M, tile_req, tv,
                          o, inv, dt, g3, Jp, Jz, fp, contact, own, gown, jvel, Pc, Pown, bad, big,
                          live ? b * a0.horizon + s_glob : -1, stamp_on);
   } else if (limb) {
@@ -833,7 +960,7 @@ __device__ __attribute__((always_inline)) inline void limb_step(LimbShared<NM, F
     {
       real P[3][3], U[3][3];
       const hs_topo* Ts = opaque_s(T);
-      limb_outer(Ts, sh.k.links[L], limb_frame(Ts, L, straight, own, W, row, u, tv[0], om), W.ktab[row][L], P, U, big);
+      limb_outer(Ts, sh.k.links[L], limb_frame(Ts, L, straight, own, W, W.kf, row, u, tv[0], om), W.ktab[row][L], P, U, big);
 #pragma unroll
       for (int kk = 0; kk < 3; kk++)
 #pragma unroll
@@ -849,7 +976,7 @@ __device__ __attribute__((always_inline)) inline void limb_step(LimbShared<NM, F
     {
       real P[3][3], U[3][3];
       const hs_topo* Ts = opaque_s(T);
-      limb_outer(Ts, sh.k.links[L], limb_frame(Ts, L, straight, own, W, row + 4, u, tv[4], op), W.ktab[row + 4][L], P, U,
+      limb_outer(Ts, sh.k.links[L], limb_frame(Ts, L, straight, own, W, W.kf, row + 4, u, tv[4], op), W.ktab[row + 4][L], P, U,
                  big);
 #pragma unroll
       for (int kk = 0; kk < 3; kk++)
@@ -863,7 +990,7 @@ __device__ __attribute__((always_inline)) inline void limb_step(LimbShared<NM, F
     STAMP(2);
     {
       const hs_topo* T = opaque_s(T_);
-      const A34 J = limb_frame(T, L, straight, own, W, row + 2, u, tv[2], oc);
+      const A34 J = limb_frame(T, L, straight, own, W, W.kf, row + 2, u, tv[2], oc);
       if (own) {  // the chain body's differences first: its three samples are dead before the links' FK
         part_dyn((real)T->mass[T->limb_own[L][0]], inv, om.P, oc.P, op.P, om.U, oc.U, op.U, gown);
         part_g(oc.P, o, gown);
@@ -932,15 +1059,15 @@ __device__ __attribute__((always_inline)) inline void limb_step(LimbShared<NM, F
     // g to LDS (the chain bodies' and the root's subtree sums read them)
 #pragma unroll
     for (int kk = 0; kk < 3; kk++)
-      for (int j = 0; j < 6; j++) S.g[T->limb_node[L][kk]][j] = g3[kk][j];
+      for (int j = 0; j < 6; j++) S.g[mk.node(L, kk)][j] = g3[kk][j];
     if (own)
-      for (int j = 0; j < 6; j++) S.g[T->limb_own[L][0]][j] = gown[j];
+      for (int j = 0; j < 6; j++) S.g[mk.own_node(L)][j] = gown[j];
     if constexpr (FORCES) {
 #pragma unroll
       for (int kk = 0; kk < 3; kk++)
-        for (int j = 0; j < 3; j++) S.p[T->limb_node[L][kk]][j] = Pc[kk][j];
+        for (int j = 0; j < 3; j++) S.p[mk.node(L, kk)][j] = Pc[kk][j];
       if (own)
-        for (int j = 0; j < 3; j++) S.p[T->limb_own[L][0]][j] = Pown[j];
+        for (int j = 0; j < 3; j++) S.p[mk.own_node(L)][j] = Pown[j];
     }
   } else if (tlane) {
     for (int j = 0; j < 6; j++) S.g[0][j] = g0[j];
@@ -981,7 +1108,7 @@ __device__ __attribute__((always_inline)) inline void limb_step(LimbShared<NM, F
   {
     const int nk = T->node[0].nkids;
     if (l < nk && l < HS_CMAX) {
-      const int c = T->node[0].kids[l], sz = T->node[c].size;
+      const int c = mk.kid(l), sz = mk.kid_size(l, c);
       real Fk[3] = {0, 0, 0}, Vk[3] = {0, 0, 0};
 #pragma unroll
       for (int r = 0; r < 8; r++)
@@ -1020,7 +1147,7 @@ __device__ __attribute__((always_inline)) inline void limb_step(LimbShared<NM, F
     return;
   }
   // ---- contact list in foot order (ftsolver's contact columns) ----
-  const int fiL = T->link[L][2].foot;
+  const int fiL = mk.foot(L);
   const uint32_t cm = grp_or((limb && contact) ? 1u << fiL : 0u);
   const int nc = __popc(cm);
   const bool mine = limb && contact;
@@ -1287,7 +1414,7 @@ __device__ __attribute__((always_inline)) inline void limb_step(LimbShared<NM, F
   if (limb) {
 #pragma unroll
     for (int kk = 0; kk < 3; kk++) {
-      const int hh = T->link[L][kk].hinge;
+      const int hh = mk.hinge(L, kk);
       real d[3], yy[3];
 #pragma unroll
       for (int rr = 0; rr < 3; rr++) {
@@ -1385,12 +1512,44 @@ __global__ __launch_bounds__(WAVE, HS_REAL_IS_FLOAT ? HS_LIMB_WAVES_F32 : HS_LIM
   fused_coords<HS_LIMB_GROUP>((int)blockIdx.x, mp.fused_w, TILE ? HS_TILE_SLOTS * limb_tile_chunks(nt, tl) : mp.fused_n, fstep,
                               q);
   const hs_topo* __restrict__ T = mp.limb_model ? T0 + mp.limb_model[q] : T0;  // a mixed plan's wavefront model
+  STAMP(18);
   {  // the link records, 8 bytes per lane and load
     const uint64_t* src = reinterpret_cast<const uint64_t*>(&T->link[0][0]);
     uint64_t* dst = reinterpret_cast<uint64_t*>(&sh.links()[0][0]);
     constexpr int NW = sizeof(hs_link[HS_LMAX][3]) / sizeof(uint64_t);
     for (int e = (int)threadIdx.x; e < NW; e += WAVE) dst[e] = src[e];
-    wave_sync();
+    if constexpr (LOOP) {
+      // the model's per-lane constants, formed by the group's first lanes: entry l is limb l's and the root's
+      // kid l's (LimbLaneK). Two dependent loads deep, once per wavefront instead of once per tile.
+      const int l = (int)threadIdx.x;
+      if (l < LG) {
+        LimbLaneK e;
+        e.m[0] = e.m[1] = e.m[2] = e.mown = real(0);
+        e.nodes = e.hf = e.kid = e.pad_ = 0;
+        if (l < T->n_limbs) {
+          const bool own = T->limb_own_n[l] > 0;
+          const int on = own ? T->limb_own[l][0] : 0;
+#pragma unroll
+          for (int kk = 0; kk < 3; kk++) {
+            const int v = T->limb_node[l][kk];
+            e.m[kk] = (real)T->mass[v];
+            e.nodes |= (uint32_t)v << (8 * kk);
+            e.hf |= (uint32_t)T->link[l][kk].hinge << (8 * kk);
+          }
+          if (own) e.mown = (real)T->mass[on];
+          e.nodes |= (uint32_t)on << 24;
+          e.hf |= (uint32_t)T->link[l][2].foot << 24;
+          e.kid = (uint32_t)own << 16;
+        }
+        if (l < T->node[0].nkids && l < HS_CMAX) {
+          const int c = T->node[0].kids[l];
+          e.kid |= (uint32_t)c | (uint32_t)T->node[c].size << 8;
+        }
+        sh.lk[l] = e;
+      }
+    } else {
+      wave_sync();
+    }
   }
   RSTAMP(16);
   STAMP(15);
@@ -1410,6 +1569,13 @@ __global__ __launch_bounds__(WAVE, HS_REAL_IS_FLOAT ? HS_LIMB_WAVES_F32 : HS_LIM
     for (int i = 0; i < 3; i++) h.u[i] = n0.Jp(i, 0);
   }
   if constexpr (LOOP) {
+    {  // the rollout's sample times and straight-gait frames (LimbRolloutK), 8 bytes per lane and load
+      const real* src = h.W->t_tab;
+      real* dst = sh.rk.t_tab;
+      constexpr int NR = sizeof(LimbRolloutK) / sizeof(real);
+      for (int e = (int)threadIdx.x; e < NR; e += WAVE) dst[e] = src[e];
+      wave_sync();  // with the link records and the lane constants above
+    }
     // the chunk's tiles in order. Between two tiles every lane meets again, whichever way it left the step
     // (a deferred step ends its group's tile, not the wavefront), and the tile's last LDS reads (S.wd, S.a)
     // come before the next tile's outer rows are written over them

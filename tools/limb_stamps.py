@@ -11,7 +11,10 @@ so no single window shows it; HS_LIMB_TILE_PLAN=0 for the parity order). A wavef
 its "further FK passes" phase lasts more than half its pass 0.
 --tile --loop TL --iter I: TL tiles per wavefront (HS_LIMB_TILE_LOOP=TL), the stamps of the wavefronts' I-th tile
 (0: the first). "tile start -> tv, o" is the step's own prelims, from the tile's start (the head's end in the
-first tile); "prelims (tv, o)" counts from the wavefront's entry, so it is the head's cost only at I = 0."""
+first tile); "prelims (tv, o)" counts from the wavefront's entry, so it is the head's cost only at I = 0.
+The two "head" rows count from the kernel's entry (slot 18): to the stamp behind the link-record copy, and to
+the first tile's start, which is the whole head with the staging of the wavefront's constants in LDS and its
+barrier (meaningful at I = 0 only; a library without slot 18 prints its clock value there)."""
 import ctypes
 import os
 import sys
@@ -28,7 +31,8 @@ PHASES = [("prelims (tv, o)", 15, 0), ("outer t-2dt FK", 0, 1), ("outer t+2dt FK
           ("contact blocks + Schur sums", 6, 7), ("6x6 + y", 7, 8), ("outputs", 8, 9), ("TOTAL", 15, 9)]
 
 
-TILE_PHASES = [("prelims (tv, o)", 15, 0), ("tile start -> tv, o", 23, 0), ("FK pass 0 (centres + requests)", 0, 1), ("further FK passes", 1, 2),
+TILE_PHASES = [("head: entry -> link copy issued", 18, 15), ("head: entry -> first tile (I = 0)", 18, 23),
+               ("prelims (tv, o)", 15, 0), ("tile start -> tv, o", 23, 0), ("FK pass 0 (centres + requests)", 0, 1), ("further FK passes", 1, 2),
                ("exchange sync + D", 2, 3)] + PHASES[4:]
 
 

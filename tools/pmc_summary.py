@@ -19,22 +19,31 @@ import statistics
 from collections import defaultdict
 
 KERNEL = "the fused step launch"
-# the fused step launch: the limb-lane kernel (round 6: 8 rollouts per wavefront) or hs_rollout_kernel's
-# FIX_DEFER instantiation (2 per wavefront)
-STEP_LAUNCH = re.compile(r"hs_limb_kernel<\d+, false>|hs_rollout_kernel<\d+, false, 1>")
-FORCES_LAUNCH = re.compile(r"hs_limb_kernel<\d+, true>|hs_rollout_kernel<\d+, true, 0>")  # solve_forces' step launches (--forces)
+# the fused step launch: the limb-lane kernel, packed (8 rollouts per wavefront: <NM, false, false>) or
+# tile-mapped (one rollout x eight steps per tile: <NM, false, true, limb_tile_desc>), or hs_rollout_kernel's
+# FIX_DEFER instantiation (2 rollouts per wavefront)
+STEP_LAUNCH = re.compile(r"hs_limb_kernel<\d+, false, (false|true, limb_tile_desc)>|hs_rollout_kernel<\d+, false, 1>")
+# solve_forces' step launches (--forces)
+FORCES_LAUNCH = re.compile(r"hs_limb_kernel<\d+, true, (false|true, limb_tile_desc)>|hs_rollout_kernel<\d+, true, 0>")
+TILE_LAUNCH = re.compile(r"hs_limb_kernel<\d+, (false|true), true, ")
 
 
-def collect(root, n_rollouts, step_launch=STEP_LAUNCH):
+def collect(root, n_rollouts, step_launch=STEP_LAUNCH, job_steps=20):
     """counter -> per-step values of the step launches of the timed job: in each pass, the dispatches with
-    the most steps (the bench's warm-up job runs fewer steps per launch and is left out)"""
+    the most steps (the bench's warm-up job runs fewer steps per launch and is left out). A tile-mapped
+    launch's grid is rollouts x chunks of tiles, which does not give its steps: its dispatches with the
+    pass's largest grid are the timed job's, of job_steps steps each (a job longer than one launch is not
+    handled)."""
     vals = defaultdict(dict)  # counter -> dispatch -> per-step value
     for path in sorted(glob.glob(os.path.join(root, "p*", "run_counter_collection.csv"))):
         with open(path) as f:
             rows = [r for r in csv.DictReader(f) if step_launch.search(r["Kernel_Name"])]
         def waves_per_step(name):
             return (n_rollouts + 7) // 8 if "hs_limb_kernel" in name else (n_rollouts + 1) // 2
-        steps_of = {r["Dispatch_Id"]: int(r.get("Grid_Size") or r.get("Grid_Size_X")) // 64 // waves_per_step(r["Kernel_Name"])
+        grid = {r["Dispatch_Id"]: int(r.get("Grid_Size") or r.get("Grid_Size_X")) // 64 for r in rows}
+        tile_grid = max((grid[r["Dispatch_Id"]] for r in rows if TILE_LAUNCH.search(r["Kernel_Name"])), default=0)
+        steps_of = {r["Dispatch_Id"]: (job_steps if grid[r["Dispatch_Id"]] == tile_grid else 0)
+                    if TILE_LAUNCH.search(r["Kernel_Name"]) else grid[r["Dispatch_Id"]] // waves_per_step(r["Kernel_Name"])
                     for r in rows}
         most = max(steps_of.values(), default=0)
         for row in rows:
@@ -88,7 +97,7 @@ def main():
     ap.add_argument("--rows-per-step", type=int, default=1,
                     help="output rows (fused steps) per bench step: the call horizon H (configs[2]: 32)")
     a = ap.parse_args()
-    v = collect(a.root, a.rollouts, FORCES_LAUNCH if a.forces else STEP_LAUNCH)
+    v = collect(a.root, a.rollouts, FORCES_LAUNCH if a.forces else STEP_LAUNCH, a.job_steps)
     v = {c: [x * a.rows_per_step for x in xs] for c, xs in v.items()}  # per bench step (H rows)
     med = {c: statistics.median(x) for c, x in v.items()}
     sha = lib_of(a.root)
@@ -107,6 +116,9 @@ def main():
                 lines.append(f"  {c:26s} {med[c] / waves:10.1f}")
         if "SQ_WAVE_CYCLES" in med and "SQ_WAIT_ANY" in med:
             lines.append(f"  wait fraction (SQ_WAIT_ANY / SQ_WAVE_CYCLES) {med['SQ_WAIT_ANY'] / med['SQ_WAVE_CYCLES']:.3f}")
+    if med.get("SQ_LDS_IDX_ACTIVE") and "SQ_LDS_BANK_CONFLICT" in med:
+        lines.append(f"LDS bank-conflict share (SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE, extra cycles over all "
+                     f"LDS-array cycles): {med['SQ_LDS_BANK_CONFLICT'] / med['SQ_LDS_IDX_ACTIVE']:.3f}")
     traffic = fp64 = None
     job_steps = a.job_steps
     if "FETCH_SIZE" in med and "WRITE_SIZE" in med:
