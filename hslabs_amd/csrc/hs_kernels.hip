@@ -3732,27 +3732,13 @@ static int launch_limb(const hs_topo* d_topo, const hs_run_args& a, void* worksp
   const int wsteps = mp.limb_tile ? HS_TILE_SLOTS * limb_tile_chunks(limb_tile_count(mp.fused_n), m.limb_tile_loop) : mp.fused_n;
   const dim3 grid((unsigned)((int64_t)m.fused_w * wsteps));
   const int nm = mp.max_parts <= 18 ? 18 : (mp.max_parts <= 22 ? 22 : HS_NMAX);
-  // the tile mapping's slot sequence (hs_limb_tile.h), a kernel argument: the planner's where it saves FK
-  // passes (tile_plan 1; 2: its chain-aligned sequence whatever it saves), else the parity order. The
-  // kernel takes the sequence as its tile descriptor: every slot's step and row and every tile's requests.
-  // (A launch no descriptor holds is routed to the packed mapping by limb_tile() in hs_capi.cpp.)
+  // the tile mapping's slot sequence as the kernel's tile descriptor (hs_limb_tile.h: limb_tile_desc_build, which
+  // reads tile_plan). (A launch no descriptor holds is routed to the packed mapping by limb_tile() in hs_capi.cpp.)
   limb_tile_desc plan = {};
   if (mp.limb_tile) {
     const limb_tile_launch L = {mp.fused_n, mp.fused_s0, mp.fused_h, a.k0, a.n_t, mp.ktab_nl > 0 ? mp.ktab_nl : HS_LMAX};
-    if (!limb_tile_desc_ok(L.n, L.h, L.k0, L.n_t) || L.s0 < 0) return (int)hipErrorInvalidValue;
-    int16_t step[HS_TILE_PLAN_STEPS];
     bool planned = false;
-    if (tile_plan == 2) {
-      int row[HS_TILE_PLAN_STEPS];
-      limb_tile_rows(L, row);
-      limb_tile_chain_fill(row, L.n, step);
-      planned = true;
-    } else if (tile_plan) {
-      planned = limb_tile_plan(L, step);
-    } else {
-      limb_tile_parity_fill(L.n, step);
-    }
-    if (!limb_tile_desc_fill(L, step, plan)) return (int)hipErrorInvalidValue;
+    if (!limb_tile_desc_build(L, tile_plan, plan, &planned)) return (int)hipErrorInvalidValue;
     if (tile_planned) *tile_planned = planned;
   }
 #define HS_LIMB_LAUNCH(NM_, FORCES_)                                                                                  \

@@ -44,6 +44,18 @@
 constexpr int LG = 8;           // lanes per rollout group
 constexpr int LGR = WAVE / LG;  // rollouts per wavefront
 
+// HS_DBG builds (tools/limb_dbg.py): value n of the step to g_dbg, 32 slots per (rollout, global step) row
+// (dbg_row: b * horizon + s_glob of the lane's group, -1 for an idle one)
+__device__ inline int dbg_row(bool live, int b, int horizon, int s_glob) { return live ? b * horizon + s_glob : -1; }
+#ifdef HS_DBG
+#define LDBG(dbg_r, slot, val, n)                                                                                \
+  do {                                                                                                           \
+    if (HS_DBG == (n) && (dbg_r) >= 0 && (size_t)(dbg_r) * 32 + (slot) < (1u << 22)) g_dbg[(size_t)(dbg_r) * 32 + (slot)] = (double)(val); \
+  } while (0)
+#else
+#define LDBG(dbg_r, slot, val, n) do {} while (0)
+#endif
+
 // steps this process's limb-lane launches deferred to the fixup launch (hs_limb_stats; one atomic per
 // deferred step, rare)
 __device__ unsigned long long g_limb_deferred;
@@ -228,6 +240,69 @@ __device__ __attribute__((always_inline)) inline void limb_outer(const hs_topo* 
   for (int kk = 0; kk < 3; kk++) fk_link<false>(T, LK[kk], kk, Jv, H, sq[kk], cq[kk], P[kk], U[kk], nul, nul, nul, nc);
 }
 
+// sh.k.outer's rows, [Pm, Um, Pp, Up][link][component], a limb lane's column each: a sample's links to the
+// minus rows (o0 = 0) or the plus rows (o0 = 18) of column col, and link kk's four vectors back
+__device__ __attribute__((always_inline)) inline void outer_put(real (&outer)[36][LGR * HS_LMAX], int o0, int col,
+                                                                const real (&P)[3][3], const real (&U)[3][3]) {
+#pragma unroll
+  for (int kk = 0; kk < 3; kk++)
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+      outer[o0 + 3 * kk + j][col] = P[kk][j];
+      outer[o0 + 9 + 3 * kk + j][col] = U[kk][j];
+    }
+}
+__device__ __attribute__((always_inline)) inline void outer_get(const real (&outer)[36][LGR * HS_LMAX], int kk, int col,
+                                                                real* Pm, real* Um, real* Pp, real* Up) {
+#pragma unroll
+  for (int j = 0; j < 3; j++) {
+    Pm[j] = outer[3 * kk + j][col];
+    Um[j] = outer[9 + 3 * kk + j][col];
+    Pp[j] = outer[18 + 3 * kk + j][col];
+    Up[j] = outer[27 + 3 * kk + j][col];
+  }
+}
+
+// a motor's joint rate at the centre (compute_vel_traj's wrapped difference of q at t + dt and t - dt), the
+// +-pi wrap as selects
+__device__ inline real wrap_rate(real q_plus, real q_minus, real dt) {
+  const real dd = q_plus - q_minus;
+  const real lo = dd - 2 * kPi, hi = dd + 2 * kPi;
+  return (dd > kPi ? lo : (dd < -kPi ? hi : dd)) / (2 * dt);
+}
+// a joint value past sincos_k_small's range at any of the stencil's three rows defers the step
+__device__ inline bool limb_rows_big(const real* qm, const real* q0, const real* qp) {
+  bool big = false;
+#pragma unroll
+  for (int kk = 0; kk < 3; kk++) big |= sincos_big(qm[kk]);
+#pragma unroll
+  for (int kk = 0; kk < 3; kk++) big |= sincos_big(q0[kk]);
+#pragma unroll
+  for (int kk = 0; kk < 3; kk++) big |= sincos_big(qp[kk]);
+  return big;
+}
+
+// the whole step to the fixup launch (hs_rollout_kernel FIX_SOLVE): the group's first lane lists it.
+// item: the rollout's slot in hs_rollout_kernel's layout (2 * wavefront + half)
+__device__ inline void limb_defer(const hs::launch_map& mp, bool live, int l, int s_glob, int item) {
+  if (l == 0 && live) {
+    atomicAdd(&g_limb_deferred, 1ull);  // hs_limb_stats
+    const int it = atomicAdd(mp.fix_count, 1);
+    mp.fix_items[2 * it] = s_glob - mp.fused_s0;  // the local step (formed here: not a register held up to here)
+    mp.fix_items[2 * it + 1] = item;
+  }
+}
+
+// the limb whose foot holds contact rank `rank` of the group's contact mask cm (foot order; 0 where none does)
+__device__ inline int rank_limb(const hs_topo* T, uint32_t cm, int nl, int rank) {
+  int src = 0;
+  for (int L2 = 0; L2 < nl; L2++) {
+    const int f2 = T->link[L2][2].foot;
+    if (((cm >> f2) & 1) && __popc(cm & ((1u << f2) - 1)) == rank) src = L2;
+  }
+  return src;
+}
+
 // A contact's first-order block D_c (packed lower: 00 10 11 20 21 22) and g_c on its limb lane
 // (fast_solve_lanes: joint m of the foot's chain, foot link first, on lane m of a quad, summed
 // ((m0 + m1) + (m2 + m3)); the chain's jointless bodies add exact zeros)
@@ -277,15 +352,7 @@ __device__ __attribute__((always_inline)) inline void limb_forces(const hs_topo*
                                                                   const real (&Pc)[3][3], const real* fp,
                                                                   const real (&xt)[3][3], bool bad, bool big) {
   const int n = T->n;
-#ifdef HS_DBG
-  const int dbg_r = live ? b * a.horizon + s_glob : -1;
-#define FDBG(slot, val, n_)                                                                                      \
-  do {                                                                                                           \
-    if (HS_DBG == (n_) && dbg_r >= 0 && (size_t)dbg_r * 32 + (slot) < (1u << 22)) g_dbg[(size_t)dbg_r * 32 + (slot)] = (double)(val); \
-  } while (0)
-#else
-#define FDBG(slot, val, n_) do {} while (0)
-#endif
+  [[maybe_unused]] const int dbg_r = dbg_row(live, b, a.horizon, s_glob);
   real ts[9];
 #pragma unroll
   for (int q = 0; q < 9; q++) ts[q] = 0;
@@ -304,7 +371,7 @@ __device__ __attribute__((always_inline)) inline void limb_forces(const hs_topo*
   opaque_vals<9>(ts);  // forces_solve keeps them in LDS (sv.y)
   const int dbg_f = T->link[L][2].foot;
   (void)dbg_f;
-  if (l == 0) FDBG(0, ts[3], 30);
+  if (l == 0) LDBG(dbg_r, 0, ts[3], 30);
   const size_t orow = (size_t)b * a.horizon + s_glob;
   // the limb's blocks (forces_solve's stages), its 27 terms of the sums over the limbs formed as soon as
   // both factors exist: K_f - S_l (packed lower), q_f + e_l -- forces_solve's fr.b - fr.a / fr.b + fr.a,
@@ -318,8 +385,8 @@ __device__ __attribute__((always_inline)) inline void limb_forces(const hs_topo*
     ForcesRows F;
     forces_rows(F, Jp, Jz, Pc, fp, o, xt, zz);
     okB = forces_foot(F, fp, o, Ct, Bd, Bl, rdB, rb);
-    FDBG(24 + dbg_f, Ct[0], 36);
-    FDBG(24 + dbg_f, rb[0], 37);
+    LDBG(dbg_r, 24 + dbg_f, Ct[0], 36);
+    LDBG(dbg_r, 24 + dbg_f, rb[0], 37);
     if (okB) {
       ForcesV G;
       forces_v(G, Ct, Bl, rdB, rb);
@@ -336,12 +403,7 @@ __device__ __attribute__((always_inline)) inline void limb_forces(const hs_topo*
   }
   const bool fast = !grp_any(limb && !okB, gbase);
   if (!fast || grp_any(big, gbase)) {  // the dense normal equations: the forces fixup's (forces_solve)
-    if (l == 0 && live) {
-      atomicAdd(&g_limb_deferred, 1ull);
-      const int it = atomicAdd(mp.fix_count, 1);
-      mp.fix_items[2 * it] = s_glob - mp.fused_s0;  // the local step (formed here: not a register held up to here)
-      mp.fix_items[2 * it + 1] = b;  // 2 * wavefront + half of hs_rollout_kernel's layout
-    }
+    limb_defer(mp, live, l, s_glob, b);
     return;
   }
   // K = W_tt - sum S_l + sum K_f, rhs = sum (q_f + e_l) - d_t
@@ -359,7 +421,7 @@ __device__ __attribute__((always_inline)) inline void limb_forces(const hs_topo*
     kv[e] = (e < 21) ? wtt_entry(e, ts, n) + tot : tot - dtv;
   }
   opaque_vals<27>(kv);  // fr.a[0] (LDS)
-  if (l == 0) FDBG(1, kv[0], 33);
+  if (l == 0) LDBG(dbg_r, 1, kv[0], 33);
   real K[36], rd[6], lam[6];
 #pragma unroll
   for (int r = 0; r < 6; r++) {
@@ -369,7 +431,7 @@ __device__ __attribute__((always_inline)) inline void limb_forces(const hs_topo*
   }
   ldl_n<6>(K, real(0), rd);  // >= I
   ldl_solve_n<6>(K, rd, lam);
-  if (l == 0) FDBG(2, lam[0], 34);
+  if (l == 0) LDBG(dbg_r, 2, lam[0], 34);
   bool nan = false;
   real t[3] = {0, 0, 0};
   if (limb) {  // y_f = B_f^-1 (r_f - C~_f^T lam)
@@ -379,7 +441,7 @@ __device__ __attribute__((always_inline)) inline void limb_forces(const hs_topo*
       t[k] = s;
     }
     ldl_solve_n<3>(Bl, rdB, t);
-    FDBG(24 + dbg_f, t[0], 35);
+    LDBG(dbg_r, 24 + dbg_f, t[0], 35);
     for (int k = 0; k < 3; k++) nan |= t[k] != t[k];
     const int f = T->link[L][2].foot;
     if (live && a.cf)
@@ -390,7 +452,6 @@ __device__ __attribute__((always_inline)) inline void limb_forces(const hs_topo*
   const bool any_nan = grp_any(nan, gbase), any_bad = grp_any(limb && bad, gbase);
   if (l == 0 && live && a.flags) a.flags[orow] = (any_nan ? HS_FLAG_NAN : 0u) | (any_bad ? HS_FLAG_UNREACH : 0u);
 }
-#undef FDBG
 
 // The tile loop's wavefront constants. What a tile reads of the model per limb lane and of the rollout's
 // record is the same in every tile of the chunk, and read from global memory it is a chain of dependent
@@ -488,16 +549,53 @@ __device__ inline real lane_push(real v, int dst) {
   }
 }
 
-// the K and D phase's HS_DBG values, as the packed mapping's LDBG writes them (dbg_r: b * horizon + s_glob of
-// the lane's group, -1 for an idle one)
-#ifdef HS_DBG
-#define TDBG(slot, val, n)                                                                                       \
-  do {                                                                                                           \
-    if (HS_DBG == (n) && dbg_r >= 0 && (size_t)dbg_r * 32 + (slot) < (1u << 22)) g_dbg[(size_t)dbg_r * 32 + (slot)] = (double)(val); \
-  } while (0)
-#else
-#define TDBG(slot, val, n) do {} while (0)
-#endif
+// What the K and D phase of either mapping leaves to the phases after it, per limb lane
+struct LimbKD {
+  real g3[3][6];  // the links' g (f, then f's torque part moved about o)
+  real Jp[3][3], Jz[3][3], fp[3];
+  bool contact = false;
+  bool own = false;  // this limb computes a chain body (limb_own_n = 1)
+  real gown[6];
+  real jvel[3];
+  real Pc[3][3], Pown[3];  // forces mode: the links' and the chain body's positions at the centre
+  bool bad = false, big = false;
+};
+
+// One link of the centre row once its FK is done, the same in both mappings: the fences where
+// hs_rollout_kernel's later phases read the features from LDS, the link's outer rows, its finite differences
+// and its g about o, with the K and D phase's HS_DBG taps. BARRIER: the packed mapping's sched_barrier ahead of
+// the outer reads.
+template <bool FORCES, bool BARRIER, bool LOOP>
+__device__ __attribute__((always_inline)) inline void limb_centre_link(
+    const LimbModelK<LOOP>& mk, const real (&outer)[36][LGR * HS_LMAX], int ol, int l, int L, int kk, real* P0, real* U0,
+    real* Jp, real* Jz, real* fp, real* Pc, const real* o, real inv, real* g, int dbg_r) {
+  opaque_vals<3>(P0);
+  if constexpr (FORCES)
+    for (int j = 0; j < 3; j++) Pc[j] = P0[j];
+  opaque_vals<3>(U0);
+  opaque_vals<3>(Jp);
+  opaque_vals<3>(Jz);
+  if (kk == 2) opaque_vals<3>(fp);
+  real Pm[3], Um[3], Pp[3], Up[3];
+  if constexpr (BARRIER) __builtin_amdgcn_sched_barrier(0);
+  outer_get(outer, kk, ol, Pm, Um, Pp, Up);
+  part_dyn(mk.mass(L, kk), inv, Pm, P0, Pp, Um, U0, Up, g);
+  [[maybe_unused]] const int node = mk.node(L, kk);  // (HS_DBG builds: the part's row)
+  LDBG(dbg_r, node, P0[0], 1);
+  LDBG(dbg_r, node, U0[0], 5);
+  LDBG(dbg_r, node, g[0], 2);
+  LDBG(dbg_r, node, g[3], 10);
+  LDBG(dbg_r, node, g[1], 13);
+  LDBG(dbg_r, node, g[2], 14);
+  LDBG(dbg_r, node, g[4], 16);
+  if (l == 0) LDBG(dbg_r, 31, o[0], 15);
+  if (l == 0) LDBG(dbg_r, 30, o[1], 15);
+  LDBG(dbg_r, node, Um[0], 9);
+  LDBG(dbg_r, node, Up[0], 11);
+  LDBG(dbg_r, node, Pm[0], 12);
+  part_g(P0, o, g);
+  LDBG(dbg_r, node, g[3], 3);
+}
 
 #ifdef HS_STAMPS
 #undef HS_STAMP_GATE
@@ -510,8 +608,7 @@ __device__ __attribute__((always_inline)) inline void limb_tile_kd(
     const hs_topo* T_, const LimbModelK<LOOP>& mk, const KinFrames& kf, const real* ttab,
     real (&outer)[36][LGR * HS_LMAX], hs_link (&links)[HS_LMAX][3], const RolloutWS& W, bool straight,
     const real* u, real v, int lane, int nl, bool limb, int L, bool live, int row0, uint32_t M, uint64_t req,
-    const real* tv, const real* o, real inv, real dt, real (&g3)[3][6], real (&Jp)[3][3], real (&Jz)[3][3], real* fp, bool& contact, bool& own,
-    real* gown, real* jvel, real (&Pc)[3][3], real* Pown, bool& bad, bool& big, int dbg_r, bool stamp_on) {
+    const real* tv, const real* o, real inv, real dt, LimbKD& kd, int dbg_r, bool stamp_on) {
   (void)dbg_r;
   (void)stamp_on;  // (HS_STAMPS builds: this tile stamps)
   const int grp = lane >> 3, l = lane & 7;
@@ -530,7 +627,7 @@ __device__ __attribute__((always_inline)) inline void limb_tile_kd(
   auto col = [](int ln) { return (ln >> 3) * HS_LMAX + (ln & 7); };  // a limb lane's column of sh.k.outer
   real P[3][3], U[3][3];  // a limb lane's links at its centre row
   BodyS om, op, oc;       // its chain body at the three rows
-  own = limb && mk.own(L);
+  kd.own = limb && mk.own(L);
   // ---- pass 0: the centre rows on the limb lanes, the first requests on the idle lanes ----
   {
     int rq = 0, fL = L;
@@ -565,29 +662,11 @@ __device__ __attribute__((always_inline)) inline void limb_tile_kd(
       A34 Jv = J, H;
 #pragma unroll
       for (int kk = 0; kk < 3; kk++)
-        fk_link<true>(T, links[fL][kk], kk, Jv, H, sq[kk], cq[kk], P[kk], U[kk], Jp[kk], Jz[kk], fp, contact);
-      if (dm >= 0) {
-        const int c = col(dm);
-#pragma unroll
-        for (int kk = 0; kk < 3; kk++)
-#pragma unroll
-          for (int j = 0; j < 3; j++) {
-            outer[3 * kk + j][c] = P[kk][j];
-            outer[9 + 3 * kk + j][c] = U[kk][j];
-          }
-      }
-      if (dp >= 0) {
-        const int c = col(dp);
-#pragma unroll
-        for (int kk = 0; kk < 3; kk++)
-#pragma unroll
-          for (int j = 0; j < 3; j++) {
-            outer[18 + 3 * kk + j][c] = P[kk][j];
-            outer[27 + 3 * kk + j][c] = U[kk][j];
-          }
-      }
+        fk_link<true>(T, links[fL][kk], kk, Jv, H, sq[kk], cq[kk], P[kk], U[kk], kd.Jp[kk], kd.Jz[kk], kd.fp, kd.contact);
+      if (dm >= 0) outer_put(outer, 0, col(dm), P, U);
+      if (dp >= 0) outer_put(outer, 18, col(dp), P, U);
     }
-    if (!limb) contact = false;
+    if (!limb) kd.contact = false;
     oc = ob;
     if (!straight) {  // (the same on every lane: one rollout)
 #pragma unroll
@@ -614,16 +693,9 @@ __device__ __attribute__((always_inline)) inline void limb_tile_kd(
       real P2[3][3], U2[3][3];
       bool nb = false;
       const hs_topo* T = opaque_s(T_);
-      limb_outer(T, links[L], limb_frame(T, L, straight, own, W, kf, frow, u, ttab[frow] * v, ob), W.ktab[frow][L], P2,
+      limb_outer(T, links[L], limb_frame(T, L, straight, kd.own, W, kf, frow, u, ttab[frow] * v, ob), W.ktab[frow][L], P2,
                  U2, nb);
-      const int c = col(dst), o0 = side ? 18 : 0;
-#pragma unroll
-      for (int kk = 0; kk < 3; kk++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-          outer[o0 + 3 * kk + j][c] = P2[kk][j];
-          outer[o0 + 9 + 3 * kk + j][c] = U2[kk][j];
-        }
+      outer_put(outer, side ? 18 : 0, col(dst), P2, U2);
     }
     if (!straight) {
 #pragma unroll
@@ -639,93 +711,109 @@ __device__ __attribute__((always_inline)) inline void limb_tile_kd(
   STAMP(2);
   wave_sync();  // every group's outer rows
   if (limb) {
-    const hs_topo* T = T_;
-    (void)T;  // (HS_DBG builds: the parts' rows)
-    if (own) {
+    if (kd.own) {
       if (straight) {  // kin_sample_straight's features: limb_frame's own expressions at the outer rows
         om = body_straight(kf.own[L][0], u, tv[0]);
         op = body_straight(kf.own[L][0], u, tv[4]);
       }
-      part_dyn(mk.mass_own(L), inv, om.P, oc.P, op.P, om.U, oc.U, op.U, gown);
-      part_g(oc.P, o, gown);
+      part_dyn(mk.mass_own(L), inv, om.P, oc.P, op.P, om.U, oc.U, op.U, kd.gown);
+      part_g(oc.P, o, kd.gown);
       if constexpr (FORCES)
-        for (int j = 0; j < 3; j++) Pown[j] = oc.P[j];
+        for (int j = 0; j < 3; j++) kd.Pown[j] = oc.P[j];
     }
     const int ol = grp * HS_LMAX + l;
 #pragma unroll
-    for (int kk = 0; kk < 3; kk++) {
-      real* P0 = P[kk];
-      real* U0 = U[kk];
-      opaque_vals<3>(P0);  // the features as hs_rollout_kernel's later phases read them (LDS)
-      if constexpr (FORCES)
-        for (int j = 0; j < 3; j++) Pc[kk][j] = P0[j];
-      opaque_vals<3>(U0);
-      opaque_vals<3>(Jp[kk]);
-      opaque_vals<3>(Jz[kk]);
-      if (kk == 2) opaque_vals<3>(fp);
-      real Pm[3], Um[3], Pp[3], Up[3];
-#pragma unroll
-      for (int j = 0; j < 3; j++) {
-        Pm[j] = outer[3 * kk + j][ol];
-        Um[j] = outer[9 + 3 * kk + j][ol];
-        Pp[j] = outer[18 + 3 * kk + j][ol];
-        Up[j] = outer[27 + 3 * kk + j][ol];
-      }
-      part_dyn(mk.mass(L, kk), inv, Pm, P0, Pp, Um, U0, Up, g3[kk]);
-      TDBG(T->limb_node[L][kk], P0[0], 1);
-      TDBG(T->limb_node[L][kk], U0[0], 5);
-      TDBG(T->limb_node[L][kk], g3[kk][0], 2);
-      TDBG(T->limb_node[L][kk], g3[kk][3], 10);
-      TDBG(T->limb_node[L][kk], g3[kk][1], 13);
-      TDBG(T->limb_node[L][kk], g3[kk][2], 14);
-      TDBG(T->limb_node[L][kk], g3[kk][4], 16);
-      if (l == 0) TDBG(31, o[0], 15);
-      if (l == 0) TDBG(30, o[1], 15);
-      TDBG(T->limb_node[L][kk], Um[0], 9);
-      TDBG(T->limb_node[L][kk], Up[0], 11);
-      TDBG(T->limb_node[L][kk], Pm[0], 12);
-      part_g(P0, o, g3[kk]);
-      TDBG(T->limb_node[L][kk], g3[kk][3], 3);
-    }
-    bad = W.kbad[row0 + 2][L] != 0;
+    for (int kk = 0; kk < 3; kk++)
+      limb_centre_link<FORCES, false>(mk, outer, ol, l, L, kk, P[kk], U[kk], kd.Jp[kk], kd.Jz[kk], kd.fp, kd.Pc[kk], o, inv, kd.g3[kk], dbg_r);
+    kd.bad = W.kbad[row0 + 2][L] != 0;
     if constexpr (LOOP) {
       // the range test's nine joint values and the joint rates' six in one batch of loads (the limb's five
-      // rows), the +-pi wrap as selects between the same doubles the branches below form: loaded pair by
-      // pair behind each joint's wrap they were three more round trips per tile
+      // rows): loaded pair by pair behind each joint's wrap they were three more round trips per tile
       real jq[5][3];
 #pragma unroll
       for (int r = 0; r < 5; r++)
 #pragma unroll
         for (int kk = 0; kk < 3; kk++) jq[r][kk] = W.ktab[row0 + r][L][kk];
+      kd.big |= limb_rows_big(jq[0], jq[2], jq[4]);
 #pragma unroll
-      for (int r = 0; r < 5; r += 2)
-#pragma unroll
-        for (int kk = 0; kk < 3; kk++) big |= sincos_big(jq[r][kk]);
-#pragma unroll
-      for (int kk = 0; kk < 3; kk++) {
-        const real dd = jq[3][kk] - jq[1][kk];
-        const real lo = dd - 2 * kPi, hi = dd + 2 * kPi;
-        jvel[kk] = (dd > kPi ? lo : (dd < -kPi ? hi : dd)) / (2 * dt);
-      }
+      for (int kk = 0; kk < 3; kk++) kd.jvel[kk] = wrap_rate(jq[3][kk], jq[1][kk], dt);
       return;
     }
-    // a joint value past sincos_k_small's range at any of the three rows defers the step
-#pragma unroll
-    for (int r = 0; r < 5; r += 2)
-#pragma unroll
-      for (int kk = 0; kk < 3; kk++) big |= sincos_big(W.ktab[row0 + r][L][kk]);
-    // the motors' joint rates at the centre (compute_vel_traj's wrapped difference of q at t +- dt)
+    kd.big |= limb_rows_big(W.ktab[row0][L], W.ktab[row0 + 2][L], W.ktab[row0 + 4][L]);
 #pragma unroll
     for (int kk = 0; kk < 3; kk++) {
       if constexpr (FORCES) break;
-      real dd = W.ktab[row0 + 3][L][kk] - W.ktab[row0 + 1][L][kk];
-      if (dd > kPi) dd -= 2 * kPi;
-      else if (dd < -kPi) dd += 2 * kPi;
-      jvel[kk] = dd / (2 * dt);
+      kd.jvel[kk] = wrap_rate(W.ktab[row0 + 3][L][kk], W.ktab[row0 + 1][L][kk], dt);
     }
   }
 }
-#undef TDBG
+
+// ---- the packed mapping's K and D phase (a limb lane's: the caller tests limb) ----
+// Liveness drives the order (the step's peak registers are here): the outer samples' pos / ust first, then the
+// centre link by link, each link's finite differences as soon as its centre values exist
+template <bool FORCES>
+__device__ __attribute__((always_inline)) inline void limb_packed_kd(
+    const hs_topo* T_, real (&outer)[36][LGR * HS_LMAX], hs_link (&links)[HS_LMAX][3], const RolloutWS& W, bool straight,
+    const real* u, int l, int L, int ol, int row, const real* tv, const real* o, real inv, real dt, LimbKD& kd, int dbg_r,
+    bool stamp_on) {
+  (void)stamp_on;  // (HS_STAMPS builds: this step stamps)
+  kd.own = T_->limb_own_n[L] > 0;
+  // the outer samples (t - 2dt, t + 2dt): the links' pos / ust to LDS (36 reals; held in registers across
+  // the centre's FK they pushed the kernel past 256 VGPRs), the chain body's pos / ust kept
+  BodyS om, op, oc;
+  {
+    real P[3][3], U[3][3];
+    const hs_topo* Ts = opaque_s(T_);
+    limb_outer(Ts, links[L], limb_frame(Ts, L, straight, kd.own, W, W.kf, row, u, tv[0], om), W.ktab[row][L], P, U, kd.big);
+    outer_put(outer, 0, ol, P, U);
+  }
+  STAMP(1);
+  // (sched_barrier: the machine scheduler would interleave the independent samples for ILP, holding
+  // two samples' FK working sets at once)
+  __builtin_amdgcn_sched_barrier(0);
+  {
+    real P[3][3], U[3][3];
+    const hs_topo* Ts = opaque_s(T_);
+    limb_outer(Ts, links[L], limb_frame(Ts, L, straight, kd.own, W, W.kf, row + 4, u, tv[4], op), W.ktab[row + 4][L], P, U,
+               kd.big);
+    outer_put(outer, 18, ol, P, U);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  STAMP(2);
+  {
+    const hs_topo* T = opaque_s(T_);
+    const A34 J = limb_frame(T, L, straight, kd.own, W, W.kf, row + 2, u, tv[2], oc);
+    if (kd.own) {  // the chain body's differences first: its three samples are dead before the links' FK
+      part_dyn((real)T->mass[T->limb_own[L][0]], inv, om.P, oc.P, op.P, om.U, oc.U, op.U, kd.gown);
+      part_g(oc.P, o, kd.gown);
+      if constexpr (FORCES)
+        for (int j = 0; j < 3; j++) kd.Pown[j] = oc.P[j];
+    }
+    const real* ja = W.ktab[row + 2][L];
+    real sq[3], cq[3];
+#pragma unroll
+    for (int kk = 0; kk < 3; kk++) {
+      kd.big |= sincos_big(ja[kk]);
+      sincos_k_small(ja[kk], &sq[kk], &cq[kk]);
+    }
+    A34 Jv = J, H;
+#pragma unroll
+    for (int kk = 0; kk < 3; kk++) {
+      real P0[3], U0[3];
+      fk_link<true>(T, links[L][kk], kk, Jv, H, sq[kk], cq[kk], P0, U0, kd.Jp[kk], kd.Jz[kk], kd.fp, kd.contact);
+      // (its sched_barrier: the link's outer values are read after its FK, not hoisted above it)
+      limb_centre_link<FORCES, true>(LimbModelK<false>{T, nullptr}, outer, ol, l, L, kk, P0, U0, kd.Jp[kk], kd.Jz[kk], kd.fp, kd.Pc[kk], o,
+                                     inv, kd.g3[kk], dbg_r);
+    }
+  }
+  kd.bad = W.kbad[row + 2][L] != 0;
+  // the motors' joint rates at the centre (compute_vel_traj's wrapped difference of q at t +- dt)
+#pragma unroll
+  for (int kk = 0; kk < 3; kk++) {
+    if constexpr (FORCES) break;
+    kd.jvel[kk] = wrap_rate(W.ktab[row + 3][L][kk], W.ktab[row + 1][L][kk], dt);
+  }
+}
 
 // FORCES: hs_run_forces_calls' solve_forces step (contact forces given motor torques, forces_solve's fast
 // path: a limb's blocks on its lane, the sums over the limbs in limb order by a DPP chain, the 6 x 6 on
@@ -911,15 +999,7 @@ __device__ __attribute__((always_inline)) inline void limb_step(LimbShared<NM, F
   } else {
     mulp(load34r(W.ktor[row0 + 2] + 6), com0, o);
   }
-#ifdef HS_DBG
-  const int dbg_r = live ? b * a0.horizon + s_glob : -1;
-#define LDBG(slot, val, n)                                                                                       \
-  do {                                                                                                           \
-    if (HS_DBG == (n) && dbg_r >= 0 && (size_t)dbg_r * 32 + (slot) < (1u << 22)) g_dbg[(size_t)dbg_r * 32 + (slot)] = (double)(val); \
-  } while (0)
-#else
-#define LDBG(slot, val, n) do {} while (0)
-#endif
+  [[maybe_unused]] const int dbg_r = dbg_row(live, b, a0.horizon, s_glob);
 
   // the torso's g (node 0; its joint frame J = I * J_A_parent, node_features), on every lane: its loads and
   // arithmetic overlap the limbs' (a torso-lane branch after them would expose its load latency)
@@ -936,122 +1016,12 @@ __device__ __attribute__((always_inline)) inline void limb_step(LimbShared<NM, F
   }
   STAMP(0);
   // ---- K and D: the limb's links and its chain body (limb lanes), the torso (lane 7) ----
-  // Liveness drives the order (the step's peak registers are here): the outer samples' pos / ust first,
-  // then the centre link by link, each link's finite differences as soon as its centre values exist
-  real g3[3][6];  // the links' g (f, then f's torque part moved about o)
-  real Jp[3][3], Jz[3][3], fp[3];
-  bool contact = false;
-  bool own = false;  // this limb computes a chain body (limb_own_n = 1)
-  real gown[6];
-  real jvel[3];
-  real Pc[3][3], Pown[3];  // forces mode: the links' and the chain body's positions at the centre
-  bool bad = false, big = false;
-  const hs_topo* const T_ = T;
+  LimbKD kd;
   if constexpr (TILE) {
-    limb_tile_kd<FORCES, LOOP>(T_, mk, *kfp, ttab, sh.k.outer, sh.links(), W, straight, u, v, lane, nl, limb, L, live, row0, tile_M, tile_req, tv,
-                         o, inv, dt, g3, Jp, Jz, fp, contact, own, gown, jvel, Pc, Pown, bad, big,
-                         live ? b * a0.horizon + s_glob : -1, stamp_on);
+    limb_tile_kd<FORCES, LOOP>(T, mk, *kfp, ttab, sh.k.outer, sh.links(), W, straight, u, v, lane, nl, limb, L, live, row0, tile_M,
+                               tile_req, tv, o, inv, dt, kd, dbg_r, stamp_on);
   } else if (limb) {
-    const int row = row0;
-    own = T->limb_own_n[L] > 0;
-    // the outer samples (t - 2dt, t + 2dt): the links' pos / ust to LDS (36 reals; held in registers across
-    // the centre's FK they pushed the kernel past 256 VGPRs), the chain body's pos / ust kept
-    BodyS om, op, oc;
-    {
-      real P[3][3], U[3][3];
-      const hs_topo* Ts = opaque_s(T);
-      limb_outer(Ts, sh.k.links[L], limb_frame(Ts, L, straight, own, W, W.kf, row, u, tv[0], om), W.ktab[row][L], P, U, big);
-#pragma unroll
-      for (int kk = 0; kk < 3; kk++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-          sh.k.outer[3 * kk + j][ol] = P[kk][j];
-          sh.k.outer[9 + 3 * kk + j][ol] = U[kk][j];
-        }
-    }
-    STAMP(1);
-    // (sched_barrier: the machine scheduler would interleave the independent samples for ILP, holding
-    // two samples' FK working sets at once)
-    __builtin_amdgcn_sched_barrier(0);
-    {
-      real P[3][3], U[3][3];
-      const hs_topo* Ts = opaque_s(T);
-      limb_outer(Ts, sh.k.links[L], limb_frame(Ts, L, straight, own, W, W.kf, row + 4, u, tv[4], op), W.ktab[row + 4][L], P, U,
-                 big);
-#pragma unroll
-      for (int kk = 0; kk < 3; kk++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-          sh.k.outer[18 + 3 * kk + j][ol] = P[kk][j];
-          sh.k.outer[27 + 3 * kk + j][ol] = U[kk][j];
-        }
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    STAMP(2);
-    {
-      const hs_topo* T = opaque_s(T_);
-      const A34 J = limb_frame(T, L, straight, own, W, W.kf, row + 2, u, tv[2], oc);
-      if (own) {  // the chain body's differences first: its three samples are dead before the links' FK
-        part_dyn((real)T->mass[T->limb_own[L][0]], inv, om.P, oc.P, op.P, om.U, oc.U, op.U, gown);
-        part_g(oc.P, o, gown);
-        if constexpr (FORCES)
-          for (int j = 0; j < 3; j++) Pown[j] = oc.P[j];
-      }
-      const real* ja = W.ktab[row + 2][L];
-      real sq[3], cq[3];
-#pragma unroll
-      for (int kk = 0; kk < 3; kk++) {
-        big |= sincos_big(ja[kk]);
-        sincos_k_small(ja[kk], &sq[kk], &cq[kk]);
-      }
-      A34 Jv = J, H;
-#pragma unroll
-      for (int kk = 0; kk < 3; kk++) {
-        real P0[3], U0[3];
-        fk_link<true>(T, sh.k.links[L][kk], kk, Jv, H, sq[kk], cq[kk], P0, U0, Jp[kk], Jz[kk], fp, contact);
-        opaque_vals<3>(P0);  // the features as hs_rollout_kernel's later phases read them (LDS)
-        if constexpr (FORCES)
-          for (int j = 0; j < 3; j++) Pc[kk][j] = P0[j];
-        opaque_vals<3>(U0);
-        opaque_vals<3>(Jp[kk]);
-        opaque_vals<3>(Jz[kk]);
-        if (kk == 2) opaque_vals<3>(fp);
-        real Pm[3], Um[3], Pp[3], Up[3];
-        __builtin_amdgcn_sched_barrier(0);  // the link's outer values read here, not hoisted above its FK
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-          Pm[j] = sh.k.outer[3 * kk + j][ol];
-          Um[j] = sh.k.outer[9 + 3 * kk + j][ol];
-          Pp[j] = sh.k.outer[18 + 3 * kk + j][ol];
-          Up[j] = sh.k.outer[27 + 3 * kk + j][ol];
-        }
-        part_dyn((real)T->mass[T->limb_node[L][kk]], inv, Pm, P0, Pp, Um, U0, Up, g3[kk]);
-        LDBG(T->limb_node[L][kk], P0[0], 1);
-        LDBG(T->limb_node[L][kk], U0[0], 5);
-        LDBG(T->limb_node[L][kk], g3[kk][0], 2);
-        LDBG(T->limb_node[L][kk], g3[kk][3], 10);
-        LDBG(T->limb_node[L][kk], g3[kk][1], 13);
-        LDBG(T->limb_node[L][kk], g3[kk][2], 14);
-        LDBG(T->limb_node[L][kk], g3[kk][4], 16);
-        if (l == 0) LDBG(31, o[0], 15);
-        if (l == 0) LDBG(30, o[1], 15);
-        LDBG(T->limb_node[L][kk], Um[0], 9);
-        LDBG(T->limb_node[L][kk], Up[0], 11);
-        LDBG(T->limb_node[L][kk], Pm[0], 12);
-        part_g(P0, o, g3[kk]);
-        LDBG(T->limb_node[L][kk], g3[kk][3], 3);
-      }
-    }
-    bad = W.kbad[row + 2][L] != 0;
-    // the motors' joint rates at the centre (compute_vel_traj's wrapped difference of q at t +- dt)
-#pragma unroll
-    for (int kk = 0; kk < 3; kk++) {
-      if constexpr (FORCES) break;
-      real dd = W.ktab[row + 3][L][kk] - W.ktab[row + 1][L][kk];
-      if (dd > kPi) dd -= 2 * kPi;
-      else if (dd < -kPi) dd += 2 * kPi;
-      jvel[kk] = dd / (2 * dt);
-    }
+    limb_packed_kd<FORCES>(T, sh.k.outer, sh.k.links, W, straight, u, l, L, ol, row0, tv, o, inv, dt, kd, dbg_r, stamp_on);
   }
   STAMP(3);
   wave_sync();  // S.g overlays sh.k: every lane's outer and link reads first
@@ -1059,15 +1029,15 @@ __device__ __attribute__((always_inline)) inline void limb_step(LimbShared<NM, F
     // g to LDS (the chain bodies' and the root's subtree sums read them)
 #pragma unroll
     for (int kk = 0; kk < 3; kk++)
-      for (int j = 0; j < 6; j++) S.g[mk.node(L, kk)][j] = g3[kk][j];
-    if (own)
-      for (int j = 0; j < 6; j++) S.g[mk.own_node(L)][j] = gown[j];
+      for (int j = 0; j < 6; j++) S.g[mk.node(L, kk)][j] = kd.g3[kk][j];
+    if (kd.own)
+      for (int j = 0; j < 6; j++) S.g[mk.own_node(L)][j] = kd.gown[j];
     if constexpr (FORCES) {
 #pragma unroll
       for (int kk = 0; kk < 3; kk++)
-        for (int j = 0; j < 3; j++) S.p[mk.node(L, kk)][j] = Pc[kk][j];
-      if (own)
-        for (int j = 0; j < 3; j++) S.p[mk.own_node(L)][j] = Pown[j];
+        for (int j = 0; j < 3; j++) S.p[mk.node(L, kk)][j] = kd.Pc[kk][j];
+      if (kd.own)
+        for (int j = 0; j < 3; j++) S.p[mk.own_node(L)][j] = kd.Pown[j];
     }
   } else if (tlane) {
     for (int j = 0; j < 6; j++) S.g[0][j] = g0[j];
@@ -1086,21 +1056,21 @@ __device__ __attribute__((always_inline)) inline void limb_step(LimbShared<NM, F
       real F[3] = {0, 0, 0}, V[3] = {0, 0, 0};
 #pragma unroll
       for (int m = kk; m < 3; m++)
-        for (int j = 0; j < 3; j++) { F[j] += g3[m][j]; V[j] += g3[m][3 + j]; }
+        for (int j = 0; j < 3; j++) { F[j] += kd.g3[m][j]; V[j] += kd.g3[m][3 + j]; }
       // particular_sub applies stage 3 in a block of its own (after a wavefront barrier): F, V enter it
       // as opaque values
       opaque_vals<3>(F);
       opaque_vals<3>(V);
       real d[3];
-      for (int j = 0; j < 3; j++) d[j] = Jp[kk][j] - o[j];
+      for (int j = 0; j < 3; j++) d[j] = kd.Jp[kk][j] - o[j];
       V[0] -= d[1] * F[2] - d[2] * F[1];
       V[1] -= d[2] * F[0] - d[0] * F[2];
       V[2] -= d[0] * F[1] - d[1] * F[0];
       for (int j = 0; j < 3; j++) xt[kk][j] = V[j];
       opaque_vals<3>(xt[kk]);  // x as the later phases read it (LDS)
-      LDBG(T->limb_node[L][kk], V[0], 4);
-      LDBG(T->limb_node[L][kk], F[0], 18);
-      LDBG(T->limb_node[L][kk], d[0], 17);
+      LDBG(dbg_r, T->limb_node[L][kk], V[0], 4);
+      LDBG(dbg_r, T->limb_node[L][kk], F[0], 18);
+      LDBG(dbg_r, T->limb_node[L][kk], d[0], 17);
     }
   }
   // the root's kids' range sums on lanes 0 .. nk - 1 of the group, in parallel (each range in preorder, as
@@ -1143,37 +1113,32 @@ __device__ __attribute__((always_inline)) inline void limb_step(LimbShared<NM, F
   const hs_run_args& a = LOOP ? opaque_k(a0) : a0;
   const hs::launch_map& mp = LOOP ? opaque_k(mp0) : mp0;
   if constexpr (FORCES) {
-    limb_forces<NM>(T, a, mp, S, limb, l, L, gbase, nl, live, b, s_glob, o, Jp, Jz, Pc, fp, xt, bad, big);
+    limb_forces<NM>(T, a, mp, S, limb, l, L, gbase, nl, live, b, s_glob, o, kd.Jp, kd.Jz, kd.Pc, kd.fp, xt, kd.bad, kd.big);
     return;
   }
   // ---- contact list in foot order (ftsolver's contact columns) ----
   const int fiL = mk.foot(L);
-  const uint32_t cm = grp_or((limb && contact) ? 1u << fiL : 0u);
+  const uint32_t cm = grp_or((limb && kd.contact) ? 1u << fiL : 0u);
   const int nc = __popc(cm);
-  const bool mine = limb && contact;
-  if (limb) LDBG(24 + fiL, fp[2], 25);
+  const bool mine = limb && kd.contact;
+  if (limb) LDBG(dbg_r, 24 + fiL, kd.fp[2], 25);
   // the limb lane holding contact rank l (lane l < nc of the group gathers that contact's values)
-  int src = 0;
-  for (int L2 = 0; L2 < nl; L2++) {
-    const int f2 = T->link[L2][2].foot;
-    if (((cm >> f2) & 1) && __popc(cm & ((1u << f2) - 1)) == l) src = L2;
-  }
-  src += gbase;
+  const int src = rank_limb(T, cm, nl, l) + gbase;
   const bool slot = l < nc;
   // joint values outside sincos_k_small's range: the fixup's
-  bool defer = grp_any(big, gbase);
+  bool defer = grp_any(kd.big, gbase);
   // a routing decision within kNearBand of its guard: HS_FLAG_NEAR_RANK, as fast_solve sets it (the values
   // are hs_rollout_kernel's bitwise, so the decisions are its own)
   bool nearf = false;
   real y3[3] = {0, 0, 0};
   real d0[3] = {0, 0, 0}, Dinv[9], gc[3], Dp6[6];
   if (mine)
-    for (int r = 0; r < 3; r++) d0[r] = o[r] - fp[r];  // A_c = [-I; [d0_c]x]
-  if (mine && nc >= 2) contact_block(Jp, Jz, xt, fp, Dp6, gc);
+    for (int r = 0; r < 3; r++) d0[r] = o[r] - kd.fp[r];  // A_c = [-I; [d0_c]x]
+  if (mine && nc >= 2) contact_block(kd.Jp, kd.Jz, xt, kd.fp, Dp6, gc);
   if (nc >= 3) {
     // zeroth_well_posed: the feet's scatter, in single precision, the contacts' d0 on lanes 0 .. nc - 1
-    float e0 = grp_getf(float(o[0] - fp[0]), src), e1 = grp_getf(float(o[1] - fp[1]), src),
-          e2 = grp_getf(float(o[2] - fp[2]), src);
+    float e0 = grp_getf(float(o[0] - kd.fp[0]), src), e1 = grp_getf(float(o[1] - kd.fp[1]), src),
+          e2 = grp_getf(float(o[2] - kd.fp[2]), src);
     if (!slot) e0 = e1 = e2 = 0.f;
     {
       const float s0 = group8_sum(e0), s1 = group8_sum(e1), s2 = group8_sum(e2);
@@ -1201,8 +1166,8 @@ __device__ __attribute__((always_inline)) inline void limb_step(LimbShared<NM, F
       const real* Dp = Dp6;
       opaque_vals<3>(d0);
       const real D[9] = {Dp[0], Dp[1], Dp[3], Dp[1], Dp[2], Dp[4], Dp[3], Dp[4], Dp[5]};
-      LDBG(24 + fiL, Dp[0], 6);
-      LDBG(24 + fiL, gc[0], 7);
+      LDBG(dbg_r, 24 + fiL, Dp[0], 6);
+      LDBG(dbg_r, 24 + fiL, gc[0], 7);
       real Lm[9];
       for (int i = 0; i < 9; i++) Lm[i] = D[i];
       real rl[3];
@@ -1286,24 +1251,14 @@ __device__ __attribute__((always_inline)) inline void limb_step(LimbShared<NM, F
         for (int j = 0; j < 3; j++) s += Dinv[3 * i + j] * t[j];
         y3[i] = -s;
       }
-      LDBG(24 + fiL, y3[0], 8);
+      LDBG(dbg_r, 24 + fiL, y3[0], 8);
       opaque_vals<3>(y3);  // sv.y
     }
   }
   if (nc == 1 || nc == 2) {
     // fast_solve_lanes' one- and two-contact closed forms (its lane 0, from FastL): here on every lane of
     // the group, the contacts' values gathered from their limb lanes
-    int s0 = 0, s1 = 0;
-    for (int L2 = 0; L2 < nl; L2++) {
-      const int f2 = T->link[L2][2].foot;
-      if ((cm >> f2) & 1) {
-        const int r2 = __popc(cm & ((1u << f2) - 1));
-        if (r2 == 0) s0 = L2;
-        if (r2 == 1) s1 = L2;
-      }
-    }
-    s0 += gbase;
-    s1 += gbase;
+    const int s0 = rank_limb(T, cm, nl, 0) + gbase, s1 = rank_limb(T, cm, nl, 1) + gbase;
     const real a[6] = {S.a[0], S.a[1], S.a[2], S.a[3], S.a[4], S.a[5]};
     bool lnear = false, ok;
     real y[6];
@@ -1317,17 +1272,17 @@ __device__ __attribute__((always_inline)) inline void limb_step(LimbShared<NM, F
         for (int r = 0; r < 6; r++) bv[i] -= a_entry(dd, r, i) * a[r];
       }
       real rl[3];
-      if (mine) LDBG(24 + fiL, M[4], 19);
-      if (mine) LDBG(24 + fiL, bv[1], 20);
+      if (mine) LDBG(dbg_r, 24 + fiL, M[4], 19);
+      if (mine) LDBG(dbg_r, 24 + fiL, bv[1], 20);
       ok = chol_n<3>(M, kFastPivotGuard, rl, lnear);
       if (ok) chol_solve_n<3>(M, rl, bv);
       for (int i = 0; i < 3; i++) y[i] = bv[i];
-      if (mine && ok) LDBG(24 + fiL, bv[0], 21);
+      if (mine && ok) LDBG(dbg_r, 24 + fiL, bv[0], 21);
     } else {  // rank 5: kernel n = (u,-u)/sqrt2 along the line between the feet
       real f0[3], f1[3], dA[2][3], Dc[2][6], gg[2][3];
       for (int r = 0; r < 3; r++) {
-        f0[r] = grp_get(fp[r], s0);
-        f1[r] = grp_get(fp[r], s1);
+        f0[r] = grp_get(kd.fp[r], s0);
+        f1[r] = grp_get(kd.fp[r], s1);
         dA[0][r] = grp_get(d0[r], s0);
         dA[1][r] = grp_get(d0[r], s1);
         gg[0][r] = grp_get(gc[r], s0);
@@ -1347,7 +1302,7 @@ __device__ __attribute__((always_inline)) inline void limb_step(LimbShared<NM, F
       if (ok) {
         for (int r = 0; r < 3; r++) { nv[r] = u[r] / un / sqrt(real(2)); nv[3 + r] = -nv[r]; }
         const bool first = mine && __popc(cm & ((1u << fiL) - 1)) == 0;
-        if (first) LDBG(24 + fiL, nv[2], 26);
+        if (first) LDBG(dbg_r, 24 + fiL, nv[2], 26);
         for (int i = 0; i < 6; i++) {
           const real* di = dA[i / 3];
           for (int j = 0; j < 6; j++) {
@@ -1360,7 +1315,7 @@ __device__ __attribute__((always_inline)) inline void limb_step(LimbShared<NM, F
           for (int r = 0; r < 6; r++) sv += a_entry(di, r, i % 3) * a[r];
           bv[i] = -sv;
         }
-        if (first) LDBG(24 + fiL, M[5], 27);
+        if (first) LDBG(dbg_r, 24 + fiL, M[5], 27);
         opaque_vals<36>(M);  // as hs_rollout_kernel's fast_solve_lanes fences them
         opaque_vals<6>(bv);
         opaque_vals<6>(nv);
@@ -1382,9 +1337,9 @@ __device__ __attribute__((always_inline)) inline void limb_step(LimbShared<NM, F
           real t = -nr / nDn;
           for (int i = 0; i < 6; i++) y[i] = bv[i] + t * nv[i];
           if (mine && __popc(cm & ((1u << fiL) - 1)) == 0) {
-            LDBG(24 + fiL, y[0], 22);
-            LDBG(24 + fiL, bv[0], 23);
-            LDBG(24 + fiL, t, 24);
+            LDBG(dbg_r, 24 + fiL, y[0], 22);
+            LDBG(dbg_r, 24 + fiL, bv[0], 23);
+            LDBG(dbg_r, 24 + fiL, t, 24);
           }
         }
       }
@@ -1398,13 +1353,8 @@ __device__ __attribute__((always_inline)) inline void limb_step(LimbShared<NM, F
     }
   }
   STAMP(8);
-  if (defer) {  // the whole step to the fixup launch (hs_rollout_kernel FIX_SOLVE)
-    if (l == 0 && live) {
-      atomicAdd(&g_limb_deferred, 1ull);  // hs_limb_stats
-      const int it = atomicAdd(mp.fix_count, 1);
-      mp.fix_items[2 * it] = s_glob - mp.fused_s0;  // the local step (formed here: not a register held up to here)
-      mp.fix_items[2 * it + 1] = mp.limb_slots ? mp.limb_slots[rslot] : b;  // 2 * wavefront + half of hs_rollout_kernel's layout
-    }
+  if (defer) {
+    limb_defer(mp, live, l, s_glob, mp.limb_slots ? mp.limb_slots[rslot] : b);
     return;
   }
 
@@ -1418,7 +1368,7 @@ __device__ __attribute__((always_inline)) inline void limb_step(LimbShared<NM, F
       real d[3], yy[3];
 #pragma unroll
       for (int rr = 0; rr < 3; rr++) {
-        d[rr] = Jp[kk][rr] - fp[rr];
+        d[rr] = kd.Jp[kk][rr] - kd.fp[rr];
         yy[rr] = mine ? y3[rr] : real(0);
       }
       real tq = real(0);
@@ -1429,9 +1379,9 @@ __device__ __attribute__((always_inline)) inline void limb_step(LimbShared<NM, F
         for (int jj = 0; jj < 3; jj++)
           if (jj != r) s = s + cross_e(d, jj, r) * yy[jj];
         real xr = xt[kk][r] + s;
-        tq = tq + Jz[kk][r] * xr;
+        tq = tq + kd.Jz[kk][r] * xr;
       }
-      real dw = tq * jvel[kk];
+      real dw = tq * kd.jvel[kk];
       S.wd[hh] = (dw > 0) ? dw : 0;
       nan |= tq != tq;
       if (live && a.tau) outp(a.tau)[orow * mp.st_tau + hh] = tq;
@@ -1453,7 +1403,7 @@ __device__ __attribute__((always_inline)) inline void limb_step(LimbShared<NM, F
     if (a.cf)
       for (int c = 3 * T->nf + l; c < mp.st_cf; c += LG) outp(a.cf)[orow * mp.st_cf + c] = real(0);
   }
-  const bool any_nan = grp_any(nan, gbase), any_bad = grp_any(limb && bad, gbase);
+  const bool any_nan = grp_any(nan, gbase), any_bad = grp_any(limb && kd.bad, gbase);
   wave_sync();
   if (l == 0 && live) {
     uint32_t flags = 0;
@@ -1472,7 +1422,6 @@ __device__ __attribute__((always_inline)) inline void limb_step(LimbShared<NM, F
   STAMP(9);
   RSTAMP(17);
 }
-#undef LDBG
 #ifdef HS_STAMPS
 #undef HS_STAMP_GATE
 #define HS_STAMP_GATE true

@@ -73,19 +73,6 @@ HS_TILE_FN int limb_tile_loop_rule(int nt, int64_t n_rollouts, int tiles, int64_
 // ---- the plan ----
 constexpr int HS_TILE_PLAN_STEPS = 256;  // the longest launch a plan holds (HS_FUSED_MAX_STEPS' default)
 
-// A slot sequence with the parity order as its default (the TILE kernels' argument before the tile
-// descriptor below; the planner's tests still read sequences through it): n_slots = 8 * limb_tile_count(n)
-// when step[] holds a plan, 0 for the parity order.
-struct limb_tile_plan_arg {
-  int32_t n_slots;
-  int16_t step[HS_TILE_PLAN_STEPS];
-};
-// the local step of a slot under the launch's sequence
-HS_TILE_FN int limb_tile_plan_step(const limb_tile_plan_arg& p, int slot, int n) {
-  if (p.n_slots == 0) return limb_tile_step(slot, n);
-  return slot >= 0 && slot < p.n_slots ? p.step[slot] : -1;
-}
-
 // a launch as the planner sees it: n local steps from global step s0 of calls of h steps, the call's
 // k0 and n_t, and the limb lanes of a group (the launch's largest model)
 struct limb_tile_launch {
@@ -97,18 +84,9 @@ HS_TILE_FN int limb_tile_row(const limb_tile_launch& L, int step) {
   const int s_glob = L.s0 + step, call = s_glob / L.h;
   return (int)(((int64_t)L.k0 + (int64_t)call * L.h) % L.n_t) + s_glob % L.h;
 }
-// row[i] = limb_tile_row(L, i) of the launch's n steps, stepping the call and its first row along
+// row[i] = limb_tile_row(L, i) of the launch's n steps
 HS_TILE_FN void limb_tile_rows(const limb_tile_launch& L, int* row) {
-  const int call = L.s0 / L.h, hm = L.h % L.n_t;
-  int pos = L.s0 % L.h, base = (int)(((int64_t)L.k0 + (int64_t)call * L.h) % L.n_t);
-  for (int i = 0; i < L.n; i++) {
-    row[i] = base + pos;
-    if (++pos == L.h) {
-      pos = 0;
-      base += hm;
-      if (base >= L.n_t) base -= L.n_t;
-    }
-  }
+  for (int i = 0; i < L.n; i++) row[i] = limb_tile_row(L, i);
 }
 
 // requests the first pass serves on the lanes idle in every group (limb_tile_kd's E0)
@@ -116,20 +94,21 @@ HS_TILE_FN int limb_tile_e0(int n_limbs) {
   return n_limbs > 0 && n_limbs < HS_TILE_SLOTS ? HS_TILE_SLOTS * (HS_TILE_SLOTS - n_limbs) / n_limbs : 0;
 }
 
-// limb_tile_kd's requests of one tile (row[]: the launch's limb_tile_rows): a live slot's minus (plus) row
-// is shared only with the live slot before (after) it in the tile whose row is exactly 2 lower (higher);
-// every other one is a request
-HS_TILE_FN int limb_tile_requests(const int* row, const int16_t* slots) {
-  int req = 0;
+// limb_tile_kd's requests of one tile (row[]: the launch's limb_tile_rows), bit 2 g slot g's minus row,
+// bit 2 g + 1 its plus row: a live slot's minus (plus) row is shared only with the live slot before (after)
+// it in the tile whose row is exactly 2 lower (higher); every other one is a request
+HS_TILE_FN uint32_t limb_tile_request_mask(const int* row, const int16_t* slots) {
+  uint32_t M = 0;
   for (int g = 0; g < HS_TILE_SLOTS; g++) {
     if (slots[g] < 0) continue;
     const int r = row[slots[g]];
     const bool shm = g > 0 && slots[g - 1] >= 0 && row[slots[g - 1]] + 2 == r;
     const bool shp = g < HS_TILE_SLOTS - 1 && slots[g + 1] >= 0 && row[slots[g + 1]] == r + 2;
-    req += !shm + !shp;
+    M |= (uint32_t)!shm << (2 * g) | (uint32_t)!shp << (2 * g + 1);
   }
-  return req;
+  return M;
 }
+HS_TILE_FN int limb_tile_requests(const int* row, const int16_t* slots) { return __builtin_popcount(limb_tile_request_mask(row, slots)); }
 
 // the further FK passes of a tile with `req` requests, and of a launch's whole sequence
 HS_TILE_FN int limb_tile_req_passes(int req, int n_limbs) {
@@ -202,31 +181,36 @@ HS_TILE_FN void limb_tile_chain_fill(const int* row, int n, int16_t* step) {
 }
 
 // The launch's sequence: the chain-aligned one where it needs fewer passes than the parity order, else
-// the parity order. Returns whether step[] holds the former. A launch longer than a plan holds keeps the
-// parity order (step[] is then not written: the caller uses limb_tile_step).
+// the parity order. Returns whether step[] holds the former.
 // *passes / *parity_passes: the further FK passes of the sequence kept and of the parity order.
-HS_TILE_FN bool limb_tile_plan(const limb_tile_launch& L, int16_t* step, int* passes = nullptr,
-                               int* parity_passes = nullptr) {
-  if (L.n < 1 || L.n > HS_TILE_PLAN_STEPS || L.h < 1 || L.n_t < 1 || L.k0 < 0 || L.s0 < 0) return false;
+HS_TILE_FN bool limb_tile_plan_rows(const int* row, int n, int n_limbs, int16_t* step, int* passes = nullptr,
+                                    int* parity_passes = nullptr) {
   int16_t par[HS_TILE_PLAN_STEPS];
-  int row[HS_TILE_PLAN_STEPS];
-  limb_tile_rows(L, row);
-  limb_tile_parity_fill(L.n, par);
-  const int pp = limb_tile_passes(row, L.n, L.n_limbs, par);
+  limb_tile_parity_fill(n, par);
+  const int pp = limb_tile_passes(row, n, n_limbs, par);
   int pc = pp;
   if (pp > 0) {  // (nothing to save otherwise: a four-limb model's E0 = 8 takes every request of most tiles)
-    limb_tile_chain_fill(row, L.n, step);
-    pc = limb_tile_passes(row, L.n, L.n_limbs, step);
+    limb_tile_chain_fill(row, n, step);
+    pc = limb_tile_passes(row, n, n_limbs, step);
   }
   if (parity_passes) *parity_passes = pp;
   if (passes) *passes = pc < pp ? pc : pp;
   if (pc < pp) return true;
-  for (int s = 0; s < HS_TILE_SLOTS * limb_tile_count(L.n); s++) step[s] = par[s];
+  for (int s = 0; s < HS_TILE_SLOTS * limb_tile_count(n); s++) step[s] = par[s];
   return false;
+}
+// the same from the launch. One longer than a plan holds keeps the parity order (step[] is then not
+// written: the caller uses limb_tile_step).
+HS_TILE_FN bool limb_tile_plan(const limb_tile_launch& L, int16_t* step, int* passes = nullptr,
+                               int* parity_passes = nullptr) {
+  if (L.n < 1 || L.n > HS_TILE_PLAN_STEPS || L.h < 1 || L.n_t < 1 || L.k0 < 0 || L.s0 < 0) return false;
+  int row[HS_TILE_PLAN_STEPS];
+  limb_tile_rows(L, row);
+  return limb_tile_plan_rows(row, L.n, L.n_limbs, step, passes, parity_passes);
 }
 
 // ---- the tile descriptor ----
-// What the TILE kernels take of a launch's slot sequence (a by-value kernel argument, built by launch_limb
+// What the TILE kernels take of a launch's slot sequence (a by-value kernel argument, limb_tile_desc_build's
 // from the sequence kept: the planner's or the parity order): per tile, every slot's local step and table
 // row, and the tile's requests. All of it is the same for every rollout of the launch, so the host forms it
 // once and the kernel reads it (limb_step, limb_tile_kd) instead of deriving it per lane and tile. What
@@ -260,39 +244,50 @@ HS_TILE_FN bool limb_tile_desc_ok(int n, int h, int k0, int n_t) {
 // one tile's entry from its eight slots (step[g], -1 idle) and the launch's steps' rows
 HS_TILE_FN void limb_tile_entry_fill(const int* row, const int16_t* slots, limb_tile_entry& e) {
   const int first = slots[0] >= 0 ? row[slots[0]] : 0;
-  uint32_t M = 0;
   for (int g = 0; g < HS_TILE_SLOTS; g++) {
     e.slot[g].step = (int16_t)(slots[g] >= 0 ? slots[g] : -1);
     e.slot[g].row = (int16_t)(slots[g] >= 0 ? row[slots[g]] : first);
-    if (slots[g] < 0) continue;
-    const int r = row[slots[g]];
-    const bool shm = g > 0 && slots[g - 1] >= 0 && row[slots[g - 1]] + 2 == r;
-    const bool shp = g < HS_TILE_SLOTS - 1 && slots[g + 1] >= 0 && row[slots[g + 1]] == r + 2;
-    M |= (uint32_t)!shm << (2 * g) | (uint32_t)!shp << (2 * g + 1);
   }
-  e.M = M;
+  e.M = limb_tile_request_mask(row, slots);
   e.nreq = 0;
   e.req = 0;
   for (int bit = 0; bit < 2 * HS_TILE_SLOTS; bit++)
-    if ((M >> bit) & 1) e.req |= (uint64_t)bit << (4 * e.nreq++);
+    if ((e.M >> bit) & 1) e.req |= (uint64_t)bit << (4 * e.nreq++);
 }
 
+// the descriptor of a sequence step[8 * limb_tile_count(n)] over the launch's rows (limb_tile_rows); the tiles
+// past the launch are idle ones: every step -1, every row 0, no request
+HS_TILE_FN void limb_tile_desc_fill_rows(const int* row, int n, const int16_t* step, limb_tile_desc& d) {
+  const int16_t idle[HS_TILE_SLOTS] = {-1, -1, -1, -1, -1, -1, -1, -1};
+  d.n_tiles = limb_tile_count(n);
+  d.pad_ = 0;
+  for (int t = 0; t < HS_TILE_DESC_TILES; t++)
+    limb_tile_entry_fill(row, t < d.n_tiles ? step + HS_TILE_SLOTS * t : idle, d.tile[t]);
+}
 // the descriptor of a launch's sequence step[8 * limb_tile_count(L.n)] (limb_tile_plan's, limb_tile_chain_fill's
 // or limb_tile_parity_fill's). False, and d untouched, where limb_tile_desc_ok says no.
 HS_TILE_FN bool limb_tile_desc_fill(const limb_tile_launch& L, const int16_t* step, limb_tile_desc& d) {
   if (!limb_tile_desc_ok(L.n, L.h, L.k0, L.n_t) || L.s0 < 0) return false;
   int row[HS_TILE_PLAN_STEPS];
-  for (int i = 0; i < L.n; i++) row[i] = limb_tile_row(L, i);
-  d.n_tiles = limb_tile_count(L.n);
-  d.pad_ = 0;
-  for (int t = 0; t < HS_TILE_DESC_TILES; t++) {
-    if (t < d.n_tiles) {
-      limb_tile_entry_fill(row, step + HS_TILE_SLOTS * t, d.tile[t]);
-    } else {
-      for (int g = 0; g < HS_TILE_SLOTS; g++) d.tile[t].slot[g].step = -1, d.tile[t].slot[g].row = 0;
-      d.tile[t].M = d.tile[t].nreq = 0;
-      d.tile[t].req = 0;
-    }
-  }
+  limb_tile_rows(L, row);
+  limb_tile_desc_fill_rows(row, L.n, step, d);
+  return true;
+}
+
+// A launch's descriptor under the sequence `mode` chooses, the rows computed once: 0 the parity order, 1 the
+// planner's choice (limb_tile_plan), 2 the chain-aligned sequence whatever it saves. *planned: whether the
+// sequence is the chain-aligned one. False, and d untouched, for a launch no descriptor holds.
+HS_TILE_FN bool limb_tile_desc_build(const limb_tile_launch& L, int mode, limb_tile_desc& d, bool* planned = nullptr) {
+  if (planned) *planned = false;
+  if (!limb_tile_desc_ok(L.n, L.h, L.k0, L.n_t) || L.s0 < 0) return false;
+  int row[HS_TILE_PLAN_STEPS];
+  int16_t step[HS_TILE_PLAN_STEPS];
+  limb_tile_rows(L, row);
+  bool chain = mode == 2;
+  if (chain) limb_tile_chain_fill(row, L.n, step);
+  else if (mode) chain = limb_tile_plan_rows(row, L.n, L.n_limbs, step);
+  else limb_tile_parity_fill(L.n, step);
+  limb_tile_desc_fill_rows(row, L.n, step, d);
+  if (planned) *planned = chain;
   return true;
 }

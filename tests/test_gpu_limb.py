@@ -14,46 +14,13 @@ nothing follows: the fp32 limb-lane kernel is not bitwise hs_rollout_kernel's, a
 fp32 tests run hs_rollout_kernel (b.run). tests/test_gpu_limb_oracle.py compares the fp32 limb-lane kernel
 with the fp64 oracle directly.
 """
-import contextlib
-import os
-
 import numpy as np
 import pytest
 
-from conftest import MODELS, transformed
+from conftest import transformed
+from limb_gpu_kit import OUTS, env, forces_tau, gpu, hmodels, run_forces, run_mixed, same  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-OUTS = ("tau", "cf", "flags", "work_cot")
-
-
-@pytest.fixture(scope="module")
-def gpu(product):
-    import torch
-
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return product
-
-
-@pytest.fixture(scope="module")
-def hmodels(gpu):
-    return {n: gpu.KinematicModel(os.path.join(MODELS, f"{n}.xml")) for n in ("hexapod", "spider", "myant")}
-
-
-@contextlib.contextmanager
-def env(**switches):
-    """the library's run-time switches (read from the environment on every call) set for the block, then
-    put back as the caller had them"""
-    old = {k: os.environ.get(k) for k in switches}
-    os.environ.update(switches)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k)
-            else:
-                os.environ[k] = v
 
 
 def run(gpu, model, params, limb, K=20, Hc=1, k0=0, best=True, dtype=None, rollout_id_base=0, steps=False,
@@ -76,13 +43,6 @@ def run(gpu, model, params, limb, K=20, Hc=1, k0=0, best=True, dtype=None, rollo
         out = {k: getattr(b, k).cpu().numpy() for k in OUTS}
         out["best_key"] = int(b.best_key.item())
         return out
-
-
-def same(a, b, what):
-    for k in ("tau", "cf", "flags", "work_cot"):
-        assert np.array_equal(a[k], b[k], equal_nan=True), \
-            f"{what}: {k} differs on {int((a[k] != b[k]).sum())} entries (max {np.nanmax(np.abs(a[k].astype(float) - b[k].astype(float))):.3e})"
-    assert a["best_key"] == b["best_key"], what
 
 
 def test_models_are_of_the_limb_lane_class(gpu, hmodels):
@@ -179,19 +139,7 @@ def test_limb_kernel_mixed_plan(gpu, hmodels, B, K, Hc, dtype):
     f32 = dtype == "f32"
 
     def go(limb):
-        with env(HS_LIMB="1" if limb else "0"):
-            mb = gpu.MixedBatch(ms, idx, params, n_t=20, k0=0, horizon=K * Hc, outputs=OUTS,
-                                dtype=torch.float32 if f32 else None)
-            for k in ("tau", "cf"):
-                getattr(mb, k).fill_(float("nan"))
-            mb.key_steps = K * Hc
-            mb.work_cot.zero_()
-            mb.reset_best()
-            mb.run_calls(K, call_horizon=Hc, best=True, accumulate=True)
-            torch.cuda.synchronize()
-            out = {k: getattr(mb, k).cpu().numpy() for k in OUTS}
-            out["best_key"] = int(mb.best_key.item())
-            return out
+        return run_mixed(gpu, ms, idx, params, dict(HS_LIMB="1" if limb else "0"), K, Hc, dtype=torch.float32 if f32 else None)
 
     n0 = gpu.api.limb_launches()
     a = go(True)
@@ -215,26 +163,17 @@ def test_limb_kernel_forces_bitwise(gpu, hmodels, name, B, K, Hc, curved, straig
     forces mode against hs_rollout_kernel's: flags and contact forces bitwise on straight gaits (both take
     the control step's subtree sums for x), within 1e-13 relative on turning gaits; the steps whose foot
     block is near singular (straight legs: the dense normal equations) deferred to the forces fixup"""
-    import torch
     from hslabs_amd import synth
 
     m = hmodels[name]
     p = synth.gen_params(B, name, id0=11, curved=curved)
     if straight_legs:  # long steps and a high torso: legs stretched to the IK's reach
         p["step_length"] *= 2.5
-    ctl = gpu.DeviceBatch(m, p, n_t=20, k0=0, horizon=K * Hc, outputs=("tau",))
-    ctl.run_calls(K, call_horizon=Hc)
-    i = torch.arange(K * Hc, device=ctl.tau.device)[None, :, None]
-    j = torch.arange(m.nmj, device=ctl.tau.device)[None, None, :]
-    tau = ctl.tau + 0.2 * torch.sin(0.7 * i + 1.3 * j)
+    tau = forces_tau(gpu, m, p, K, Hc)
 
     def go(limb):
-        with env(HS_LIMB="1" if limb else "0"):
-            fb = gpu.DeviceBatch(m, p, n_t=20, k0=0, horizon=K * Hc, outputs=("cf", "flags"))
-            fb.cf.fill_(float("nan"))
-            fb.forces_launcher(tau, K, call_horizon=Hc)()
-            torch.cuda.synchronize()
-            return fb.cf.cpu().numpy(), fb.flags.cpu().numpy()
+        r = run_forces(gpu, m, p, tau, dict(HS_LIMB="1" if limb else "0"), K, Hc)
+        return r["cf"], r["flags"]
 
     n0, d0 = gpu.api.limb_launches(), gpu.api.limb_deferred()
     ca, fa = go(True)

@@ -33,80 +33,26 @@ per step, tests/test_gpu.py; median 1e-5, tests/test_gpu_parity.py):
     disagree. Measured on the CPU: they disagree on 0 steps of every batch here except the tilted records'
     (case f: 41 of 4060 steps, 1.0 %; cap 2 %, tests/test_gpu_rec_transform.py's for tilted hexapods).
 """
-import contextlib
-import os
-
 import numpy as np
 import pytest
 
-from conftest import MODELS, record_to_oracle_gait, transformed
+from conftest import record_to_oracle_gait, transformed
+from limb_gpu_kit import OUTS, counted, fused_calls, gpu, hmodels, product_route  # noqa: F401
 from test_gpu_parity import (FP32_TOL, TAU_ABS, check_fast_every_step, check_flags, compare, near, npy,
                              reference_agreement, threads)
 
 pytestmark = pytest.mark.gpu
 
-OUTS = ("tau", "cf", "flags", "work_cot")
 N_T = 20
 BAND = 1e-5     # m: the oracle's contact decision counts as marginal within this of rcap + 1e-4
 MAX_BAND = 0.01  # the oracle's own in-band share of a batch's steps
 
 
-@pytest.fixture(scope="module")
-def gpu(product):
-    import torch
-
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return product
-
-
-@pytest.fixture(scope="module")
-def hmodels(gpu):
-    return {n: gpu.KinematicModel(os.path.join(MODELS, f"{n}.xml")) for n in ("hexapod", "spider", "myant")}
-
-
-@contextlib.contextmanager
-def env(**switches):
-    """the product's route: every HS_LIMB* switch (HS_LIMB_TILE* among them) taken out of the environment
-    for the block, `switches` set, and the environment put back as the caller had it"""
-    keys = {k for k in os.environ if k.startswith("HS_LIMB")} | set(switches)
-    old = {k: os.environ.get(k) for k in keys}
-    for k in keys:
-        os.environ.pop(k, None)
-    os.environ.update(switches)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
-def counters(gpu):
-    return np.array([gpu.api.limb_launches(), gpu.api.limb_tile_launches(), gpu.api.limb_deferred()])
-
-
 def fused(gpu, make, K, Hc, nan_fill=False):
     """K fused calls of Hc steps (hs_run_calls / hs_run_mixed_calls) with the best key on the batch make()
-    builds, no switch set: the outputs on the host, the raw key, and how far the launch counters moved"""
-    import torch
-
-    with env():
-        c0 = counters(gpu)
-        b = make()
-        if nan_fill:
-            for k in ("tau", "cf"):
-                getattr(b, k).fill_(float("nan"))
-        b.key_steps = K * Hc
-        b.work_cot.zero_()
-        b.reset_best()
-        b.run_calls(K, call_horizon=Hc, best=True, accumulate=True)
-        torch.cuda.synchronize()
-        out = {k: npy(getattr(b, k)) for k in OUTS}
-        out["best_key"] = int(b.best_key.item())
-        out["limb"], out["tile"], out["deferred"] = (int(v) for v in counters(gpu) - c0)
-    return out
+    builds, on the product's route (no HS_LIMB* switch in the environment): the outputs on the host, the raw
+    key, and how far the launch counters moved"""
+    return fused_calls(gpu, make, product_route(), K, Hc, nan_fill)
 
 
 def contact_sets(cf, nf):
@@ -203,8 +149,8 @@ def against_oracle(what, g, oracle_mod, omodel, gaits, rcap, segs, max_excluded=
     cmp = ~left & ~excl
     print(f"{what}: {int(cmp.sum())} of {cmp.size} steps compared, {int(left.sum())} left out (contact band; the "
           f"oracle alone has {100 * share:.3f} % in it), {int(flagged.sum())} flagged HS_FLAG_NEAR_RANK of which "
-          f"{int(excl.sum())} excluded (tree and ortho disagree); limb_launches +{g['limb']}, limb_tile_launches "
-          f"+{g['tile']}, limb_deferred +{g['deferred']}")
+          f"{int(excl.sum())} excluded (tree and ortho disagree); limb_launches +{g['limb_launches']}, limb_tile_launches "
+          f"+{g['tile_launches']}, limb_deferred +{g['deferred']}")
     assert excl.mean() <= max_excluded, f"{what}: {100 * excl.mean():.3f} % excluded (limit {100 * max_excluded} %)"
     # 4. flags
     check_flags(flags, r["flags"], what, ~cmp)
@@ -271,7 +217,7 @@ def test_fp32_limb_kernel_matches_fp64_oracle(gpu, hmodels, oracle_mod, omodels,
         p, _ = transformed(p, np.random.default_rng(17), tilt=tilt)
     g = fused(gpu, lambda: gpu.DeviceBatch(hmodels[name], p, n_t=N_T, k0=k0, horizon=K * Hc, outputs=OUTS,
                                            dtype=torch.float32), K, Hc)
-    assert g["limb"] > 0 and g["tile"] == 0, "the fp32 route is the packed limb-lane kernel"
+    assert g["limb_launches"] > 0 and g["tile_launches"] == 0, "the fp32 route is the packed limb-lane kernel"
     if case.startswith("f"):
         assert g["deferred"] > 0, "the tilted records must defer steps to the fixup launch"
     gaits = [record_to_oracle_gait(oracle_mod, r) for r in p]
@@ -293,7 +239,7 @@ def test_fp32_limb_kernel_mixed_plan_matches_fp64_oracle(gpu, hmodels, oracle_mo
     ms = [hmodels[n] for n in synth.MIXED_MODELS]
     g = fused(gpu, lambda: gpu.MixedBatch(ms, idx, params, n_t=N_T, k0=0, horizon=K * Hc, outputs=OUTS,
                                           dtype=torch.float32), K, Hc, nan_fill=True)
-    assert g["limb"] > 0 and g["tile"] == 0
+    assert g["limb_launches"] > 0 and g["tile_launches"] == 0
     for k, name in enumerate(synth.MIXED_MODELS):
         sel = np.nonzero(idx == k)[0]
         m = hmodels[name]
@@ -313,15 +259,14 @@ def test_fp32_limb_kernel_online_matches_fp64_oracle(gpu, hmodels, oracle_mod, o
 
     name, B, Hc, K = "myant", 37, 4, 3
     p = synth.gen_params(B, name, id0=31, curved=True)
-    with env(HS_LIMB_ONLINE="1"):
-        c0 = counters(gpu)
+    with counted(gpu, product_route(HS_LIMB_ONLINE="1")) as c:
         b = gpu.DeviceBatch(hmodels[name], p, n_t=N_T, k0=0, horizon=Hc, outputs=OUTS, dtype=torch.float32)
         b.work_cot.zero_()
         b.run_steps(K, best=False, accumulate=False)
         torch.cuda.synchronize()
         g = {k: npy(getattr(b, k)) for k in OUTS}
-        g["limb"], g["tile"], g["deferred"] = (int(v) for v in counters(gpu) - c0)
-    assert g["limb"] == K and g["tile"] == 0
+    g.update(c)
+    assert g["limb_launches"] == K and g["tile_launches"] == 0
     gaits = [record_to_oracle_gait(oracle_mod, r) for r in p]
     against_oracle("online myant", g, oracle_mod, omodels[name], gaits, hmodels[name].rcap, [((K - 1) * Hc, Hc)],
                    work=False)
@@ -339,8 +284,8 @@ def test_default_route_tile_launch_matches_oracle(gpu, hmodels, oracle_mod, omod
     B, K = 11, 40
     p = synth.gen_params(B, name, id0=5)
     g = fused(gpu, lambda: gpu.DeviceBatch(hmodels[name], p, n_t=N_T, k0=0, horizon=K, outputs=OUTS), K, 1)
-    print(f"{name}: limb_launches +{g['limb']}, limb_tile_launches +{g['tile']}, limb_deferred +{g['deferred']}")
-    assert g["tile"] > 0, "a 40-step fp64 launch takes the tile mapping by the committed rule"
+    print(f"{name}: limb_launches +{g['limb_launches']}, limb_tile_launches +{g['tile_launches']}, limb_deferred +{g['deferred']}")
+    assert g["tile_launches"] > 0, "a 40-step fp64 launch takes the tile mapping by the committed rule"
     gaits = [record_to_oracle_gait(oracle_mod, r) for r in p]
     f = oracle_mod.batch(omodels[name], gaits, N_T, 0, K, basis=oracle_mod.BASIS_FAST, n_threads=threads())
     check_fast_every_step(f"tile {name}", g, f)

@@ -12,77 +12,19 @@ two launch chunks, forces mode, fp32. The tile runs set HS_LIMB_TILE_MIN=1 so th
 takes the tile mapping whatever the routing rule is; test_routing_rule checks the rule itself with the
 switch unset.
 """
-import contextlib
+import functools
 import os
 
 import numpy as np
 import pytest
 
-from conftest import MODELS, transformed
+from conftest import transformed
+import limb_gpu_kit as kit
+from limb_gpu_kit import PACKED, ROLLOUT, TILE, forces_tau, gpu, hmodels, run_forces, run_mixed, same  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-OUTS = ("tau", "cf", "flags", "work_cot")
-# the library's switches per mapping
-TILE = dict(HS_LIMB="1", HS_LIMB_TILE="1", HS_LIMB_TILE_MIN="1")
-PACKED = dict(HS_LIMB="1", HS_LIMB_TILE="0")
-ROLLOUT = dict(HS_LIMB="0")
-
-
-@pytest.fixture(scope="module")
-def gpu(product):
-    import torch
-
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return product
-
-
-@pytest.fixture(scope="module")
-def hmodels(gpu):
-    return {n: gpu.KinematicModel(os.path.join(MODELS, f"{n}.xml")) for n in ("hexapod", "spider", "myant")}
-
-
-@contextlib.contextmanager
-def env(**switches):
-    """the library's run-time switches (read from the environment on every call) set for the block, then
-    put back as the caller had them"""
-    old = {k: os.environ.get(k) for k in switches}
-    os.environ.update(switches)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k)
-            else:
-                os.environ[k] = v
-
-
-def run(gpu, model, params, mode, K=20, Hc=1, k0=0, dtype=None, **more):
-    """K fused calls of Hc steps on the mapping `mode`; the outputs, the key, and how many tile launches and
-    deferred steps the run made"""
-    import torch
-
-    with env(**mode, **more):
-        t0, d0 = gpu.api.limb_tile_launches(), gpu.api.limb_deferred()
-        b = gpu.DeviceBatch(model, params, n_t=20, k0=k0, horizon=K * Hc, outputs=OUTS, dtype=dtype)
-        b.key_steps = K * Hc
-        b.work_cot.zero_()
-        b.reset_best()
-        b.run_calls(K, call_horizon=Hc, best=True, accumulate=True)
-        torch.cuda.synchronize()
-        out = {k: getattr(b, k).cpu().numpy() for k in OUTS}
-        out["best_key"] = int(b.best_key.item())
-        out["tile_launches"] = gpu.api.limb_tile_launches() - t0
-        out["deferred"] = gpu.api.limb_deferred() - d0
-        return out
-
-
-def same(a, b, what):
-    for k in OUTS:
-        assert np.array_equal(a[k], b[k], equal_nan=True), \
-            f"{what}: {k} differs on {int((a[k] != b[k]).sum())} entries (max {np.nanmax(np.abs(a[k].astype(float) - b[k].astype(float))):.3e})"
-    assert a["best_key"] == b["best_key"], what
+run = functools.partial(kit.run, K=20)  # K fused calls of Hc steps on the mapping `mode`: the outputs, the key, the counters
 
 
 def three_ways(gpu, model, params, what, **kw):
@@ -162,27 +104,13 @@ def test_transformed_records(gpu, hmodels, barrier):
 
 def test_mixed_plan(gpu, hmodels):
     """myant + hexapod through MixedBatch: the wavefront's model and its rollout from the plan's tables"""
-    import torch
     from hslabs_amd import synth
 
     params, idx = synth.gen_mixed(24)
     ms = [hmodels[n] for n in synth.MIXED_MODELS]
 
     def go(mode):
-        with env(**mode):
-            t0 = gpu.api.limb_tile_launches()
-            mb = gpu.MixedBatch(ms, idx, params, n_t=20, k0=0, horizon=20, outputs=OUTS)
-            for k in ("tau", "cf"):
-                getattr(mb, k).fill_(float("nan"))
-            mb.key_steps = 20
-            mb.work_cot.zero_()
-            mb.reset_best()
-            mb.run_calls(20, call_horizon=1, best=True, accumulate=True)
-            torch.cuda.synchronize()
-            out = {k: getattr(mb, k).cpu().numpy() for k in OUTS}
-            out["best_key"] = int(mb.best_key.item())
-            out["tile_launches"] = gpu.api.limb_tile_launches() - t0
-            return out
+        return run_mixed(gpu, ms, idx, params, mode, 20)
 
     t, p, r = go(TILE), go(PACKED), go(ROLLOUT)
     assert t["tile_launches"] > 0 and p["tile_launches"] == 0 and r["tile_launches"] == 0
@@ -202,25 +130,15 @@ def test_two_launch_chunks(gpu, hmodels):
 
 def test_forces_mode(gpu, hmodels):
     """solve_forces through the tile mapping against the packed one: contact forces and flags bitwise"""
-    import torch
     from hslabs_amd import synth
 
     m, B, K = hmodels["hexapod"], 9, 20
     p = synth.gen_params(B, "hexapod", id0=11)
-    ctl = gpu.DeviceBatch(m, p, n_t=20, k0=0, horizon=K, outputs=("tau",))
-    ctl.run_calls(K, call_horizon=1)
-    i = torch.arange(K, device=ctl.tau.device)[None, :, None]
-    j = torch.arange(m.nmj, device=ctl.tau.device)[None, None, :]
-    tau = ctl.tau + 0.2 * torch.sin(0.7 * i + 1.3 * j)
+    tau = forces_tau(gpu, m, p, K)
 
     def go(mode):
-        with env(**mode):
-            t0 = gpu.api.limb_tile_launches()
-            fb = gpu.DeviceBatch(m, p, n_t=20, k0=0, horizon=K, outputs=("cf", "flags"))
-            fb.cf.fill_(float("nan"))
-            fb.forces_launcher(tau, K, call_horizon=1)()
-            torch.cuda.synchronize()
-            return fb.cf.cpu().numpy(), fb.flags.cpu().numpy(), gpu.api.limb_tile_launches() - t0
+        r = run_forces(gpu, m, p, tau, mode, K)
+        return r["cf"], r["flags"], r["tile_launches"]
 
     ct, ft, nt = go(TILE)
     cp, fp_, np_ = go(PACKED)

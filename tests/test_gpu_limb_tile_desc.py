@@ -9,85 +9,18 @@ FK pass, a start inside the gait period, idle slots, calls of H > 1, a turning g
 ds_permute, in the pass the descriptor's requests say), four limbs with tier-2 deferrals (E0 = 8), a mixed
 plan (4- and 6-limb wavefronts under one descriptor), two launches, the parity order and the forced chain order through the same descriptor, 1, 3
 and 5 tiles per wavefront, forces mode, and the fp32 build (not bitwise: test_gpu_limb_tile.py's bound)."""
-import contextlib
-import os
+import functools
 
 import numpy as np
 import pytest
 
-from conftest import MODELS
+import limb_gpu_kit as kit
+from limb_gpu_kit import PACKED, TILE, forces_tau, gpu, hmodels  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-OUTS = ("tau", "cf", "flags", "work_cot")
-TILE = dict(HS_LIMB="1", HS_LIMB_TILE="1", HS_LIMB_TILE_MIN="1")
-PACKED = dict(HS_LIMB="1", HS_LIMB_TILE="0")
-
-
-@pytest.fixture(scope="module")
-def gpu(product):
-    import torch
-
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return product
-
-
-@pytest.fixture(scope="module")
-def hmodels(gpu):
-    return {n: gpu.KinematicModel(os.path.join(MODELS, f"{n}.xml")) for n in ("hexapod", "spider", "myant")}
-
-
-@contextlib.contextmanager
-def env(**switches):
-    """the library's run-time switches (read from the environment on every call) set for the block, then put
-    back as the caller had them"""
-    old = {k: os.environ.get(k) for k in switches}
-    os.environ.update(switches)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k)
-            else:
-                os.environ[k] = v
-
-
-@contextlib.contextmanager
-def counted(gpu, mode, **more):
-    c = {}
-    with env(**mode, **more):
-        t0, p0, d0 = gpu.api.limb_tile_launches(), gpu.api.limb_tile_plan_launches(), gpu.api.limb_deferred()
-        yield c
-        c["tile_launches"] = gpu.api.limb_tile_launches() - t0
-        c["plan_launches"] = gpu.api.limb_tile_plan_launches() - p0
-        c["deferred"] = gpu.api.limb_deferred() - d0
-
-
-def run(gpu, model, params, mode, K=40, Hc=1, k0=0, dtype=None, **more):
-    """K fused calls of Hc steps under `mode`: the outputs, the key and the counters"""
-    import torch
-
-    with counted(gpu, mode, **more) as c:
-        b = gpu.DeviceBatch(model, params, n_t=20, k0=k0, horizon=K * Hc, outputs=OUTS, dtype=dtype)
-        b.key_steps = K * Hc
-        b.work_cot.zero_()
-        b.reset_best()
-        b.run_calls(K, call_horizon=Hc, best=True, accumulate=True)
-        torch.cuda.synchronize()
-        out = {k: getattr(b, k).cpu().numpy() for k in OUTS}
-        out["best_key"] = int(b.best_key.item())
-    out.update(c)
-    return out
-
-
-def same(a, b, what, outs=OUTS):
-    for k in outs:
-        assert np.array_equal(a[k], b[k], equal_nan=True), \
-            f"{what}: {k} differs on {int((a[k] != b[k]).sum())} entries (max {np.nanmax(np.abs(a[k].astype(float) - b[k].astype(float))):.3e})"
-    if "best_key" in a:
-        assert a["best_key"] == b["best_key"], what
-    assert a["deferred"] == b["deferred"], f"{what}: {a['deferred']} steps deferred against {b['deferred']}"
+run = functools.partial(kit.run, K=40)  # K fused calls of Hc steps under `mode`: the outputs, the key and the counters
+same = functools.partial(kit.same, deferred=True)  # and the same number of deferred steps
 
 
 def tile_vs_packed(gpu, model, params, what, modes=(TILE,), **kw):
@@ -163,26 +96,13 @@ def test_myant_defers_the_same_steps(gpu, hmodels):
 def test_mixed_plan(gpu, hmodels):
     """myant + hexapod through MixedBatch: 4- and 6-limb wavefronts read one descriptor, E0 and the pass of a
     request from the wavefront's own model"""
-    import torch
     from hslabs_amd import synth
 
     params, idx = synth.gen_mixed(24)
     ms = [hmodels[n] for n in synth.MIXED_MODELS]
 
     def go(mode):
-        with counted(gpu, mode) as c:
-            mb = gpu.MixedBatch(ms, idx, params, n_t=20, k0=0, horizon=40, outputs=OUTS)
-            for k in ("tau", "cf"):
-                getattr(mb, k).fill_(float("nan"))
-            mb.key_steps = 40
-            mb.work_cot.zero_()
-            mb.reset_best()
-            mb.run_calls(40, call_horizon=1, best=True, accumulate=True)
-            torch.cuda.synchronize()
-            out = {k: getattr(mb, k).cpu().numpy() for k in OUTS}
-            out["best_key"] = int(mb.best_key.item())
-        out.update(c)
-        return out
+        return kit.run_mixed(gpu, ms, idx, params, mode, 40)
 
     t, pk = go(TILE), go(PACKED)
     assert t["tile_launches"] > 0 and pk["tile_launches"] == 0
@@ -217,26 +137,14 @@ def test_every_sequence_and_every_loop_length(gpu, hmodels):
 
 def test_forces_mode(gpu, hmodels):
     """solve_forces through the descriptor against the packed mapping: contact forces and flags bitwise"""
-    import torch
     from hslabs_amd import synth
 
     m, B, K = hmodels["hexapod"], 9, 40
     p = synth.gen_params(B, "hexapod", id0=11)
-    ctl = gpu.DeviceBatch(m, p, n_t=20, k0=0, horizon=K, outputs=("tau",))
-    ctl.run_calls(K, call_horizon=1)
-    i = torch.arange(K, device=ctl.tau.device)[None, :, None]
-    j = torch.arange(m.nmj, device=ctl.tau.device)[None, None, :]
-    tau = ctl.tau + 0.2 * torch.sin(0.7 * i + 1.3 * j)
+    tau = forces_tau(gpu, m, p, K)
 
     def go(mode):
-        with counted(gpu, mode) as c:
-            fb = gpu.DeviceBatch(m, p, n_t=20, k0=0, horizon=K, outputs=("cf", "flags"))
-            fb.cf.fill_(float("nan"))
-            fb.forces_launcher(tau, K, call_horizon=1)()
-            torch.cuda.synchronize()
-            out = dict(cf=fb.cf.cpu().numpy(), flags=fb.flags.cpu().numpy())
-        out.update(c)
-        return out
+        return kit.run_forces(gpu, m, p, tau, mode, K)
 
     t, pk = go(TILE), go(PACKED)
     assert t["tile_launches"] > 0 and pk["tile_launches"] == 0

@@ -8,95 +8,24 @@ tile route are BITWISE those of the packed mapping (HS_LIMB_TILE=0) and of hs_ro
 launches are counted. Every case runs HS_LIMB_TILE_LOOP = 1, 2 and 5: the same kernel with one, two and all
 five tiles behind one head (hs_limb_tile_loop_launches counts a launch whose wavefronts run more than one tile,
 so it rises with the runs at 2 and 5; the run at 1 is pinned by its tile launches)."""
-import contextlib
-import os
+import functools
 
 import numpy as np
 import pytest
 
-from conftest import MODELS, transformed
+from conftest import transformed
+import limb_gpu_kit as kit
+from limb_gpu_kit import PACKED, ROLLOUT, TILE, gpu, hmodels  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-OUTS = ("tau", "cf", "flags", "work_cot")
-TILE = dict(HS_LIMB="1", HS_LIMB_TILE="1", HS_LIMB_TILE_MIN="1")
-PACKED = dict(HS_LIMB="1", HS_LIMB_TILE="0")
-ROLLOUT = dict(HS_LIMB="0")
 TLS = (1, 2, 5)
+run = functools.partial(kit.run, K=40)  # K fused calls of Hc steps under `mode`: the outputs, the key and the counters
+same = functools.partial(kit.same, deferred=True)  # and, unless deferred=False, the same number of deferred steps
 
 
 def loop(tl, **more):
     return dict(TILE, HS_LIMB_TILE_LOOP=str(tl), **more)
-
-
-@pytest.fixture(scope="module")
-def gpu(product):
-    import torch
-
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return product
-
-
-@pytest.fixture(scope="module")
-def hmodels(gpu):
-    return {n: gpu.KinematicModel(os.path.join(MODELS, f"{n}.xml")) for n in ("hexapod", "myant")}
-
-
-@contextlib.contextmanager
-def env(**switches):
-    """the library's run-time switches (read from the environment on every call) set for the block, then put
-    back as the caller had them"""
-    old = {k: os.environ.get(k) for k in switches}
-    os.environ.update(switches)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k)
-            else:
-                os.environ[k] = v
-
-
-@contextlib.contextmanager
-def counted(gpu, mode):
-    c = {}
-    with env(**mode):
-        t0, l0, d0 = gpu.api.limb_tile_launches(), gpu.api.limb_tile_loop_launches(), gpu.api.limb_deferred()
-        yield c
-        c["tile_launches"] = gpu.api.limb_tile_launches() - t0
-        c["loop_launches"] = gpu.api.limb_tile_loop_launches() - l0
-        c["deferred"] = gpu.api.limb_deferred() - d0
-
-
-def collect(b, c):
-    out = {k: getattr(b, k).cpu().numpy() for k in OUTS}
-    out["best_key"] = int(b.best_key.item())
-    out.update(c)
-    return out
-
-
-def run(gpu, model, params, mode, K=40, Hc=1, k0=0, n_t=20):
-    """K fused calls of Hc steps under `mode`: the outputs, the key and the counters"""
-    import torch
-
-    with counted(gpu, mode) as c:
-        b = gpu.DeviceBatch(model, params, n_t=n_t, k0=k0, horizon=K * Hc, outputs=OUTS)
-        b.key_steps = K * Hc
-        b.work_cot.zero_()
-        b.reset_best()
-        b.run_calls(K, call_horizon=Hc, best=True, accumulate=True)
-        torch.cuda.synchronize()
-    return collect(b, c)
-
-
-def same(a, b, what, deferred=True):
-    for k in OUTS:
-        assert np.array_equal(a[k], b[k], equal_nan=True), \
-            f"{what}: {k} differs on {int((a[k] != b[k]).sum())} entries (max {np.nanmax(np.abs(a[k].astype(float) - b[k].astype(float))):.3e})"
-    assert a["best_key"] == b["best_key"], what
-    if deferred:
-        assert a["deferred"] == b["deferred"], f"{what}: {a['deferred']} steps deferred against {b['deferred']}"
 
 
 def check(go, what, more=None):
@@ -190,7 +119,6 @@ def test_myant_defers_inside_a_chunk(gpu, hmodels):
 
 def test_mixed_plan(gpu, hmodels):
     """myant + hexapod, B = 16: wavefronts of one launch carry different lane blocks"""
-    import torch
     from hslabs_amd import synth
 
     params, idx = synth.gen_mixed(16)
@@ -198,16 +126,7 @@ def test_mixed_plan(gpu, hmodels):
     ms = [hmodels[n] for n in synth.MIXED_MODELS]
 
     def go(mode):
-        with counted(gpu, mode) as c:
-            mb = gpu.MixedBatch(ms, idx, params, n_t=20, k0=0, horizon=40, outputs=OUTS)
-            for k in ("tau", "cf"):
-                getattr(mb, k).fill_(float("nan"))
-            mb.key_steps = 40
-            mb.work_cot.zero_()
-            mb.reset_best()
-            mb.run_calls(40, call_horizon=1, best=True, accumulate=True)
-            torch.cuda.synchronize()
-        return collect(mb, c)
+        return kit.run_mixed(gpu, ms, idx, params, mode, 40)
 
     runs, _ = check(go, "mixed B=16 K=40")
     assert np.isfinite(runs[5]["tau"]).all() and np.isfinite(runs[5]["cf"]).all()

@@ -9,18 +9,14 @@ nothing, as on myant, whose four limbs leave room for every request in the first
 on the planner's sequence: every tile launch of the forced run, none of the parity and packed runs. All tile runs set HS_LIMB_TILE_MIN=1, so every launch
 length takes the tile mapping. The shapes are test_gpu_limb_tile.py's, at lengths where the planner's sequence
 differs from the parity order (K = 40: four full chains' tiles and a tail tile of four segments)."""
-import contextlib
-import os
-
 import numpy as np
 import pytest
 
-from conftest import MODELS
+import limb_gpu_kit as kit
+from limb_gpu_kit import TILE, forces_tau, gpu, hmodels, same  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-OUTS = ("tau", "cf", "flags", "work_cot")
-TILE = dict(HS_LIMB="1", HS_LIMB_TILE="1", HS_LIMB_TILE_MIN="1")
 # the four runs: the library's switches (None: not in the environment)
 MODES = {
     "default": dict(TILE, HS_LIMB_TILE_PLAN=None),
@@ -30,75 +26,9 @@ MODES = {
 }
 
 
-@pytest.fixture(scope="module")
-def gpu(product):
-    import torch
-
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return product
-
-
-@pytest.fixture(scope="module")
-def hmodels(gpu):
-    return {n: gpu.KinematicModel(os.path.join(MODELS, f"{n}.xml")) for n in ("hexapod", "spider", "myant")}
-
-
-@contextlib.contextmanager
-def env(**switches):
-    """the library's run-time switches (read from the environment on every call) set or, at None, removed for
-    the block, then put back as the caller had them"""
-    old = {k: os.environ.get(k) for k in switches}
-    for k, v in switches.items():
-        if v is None:
-            os.environ.pop(k, None)
-        else:
-            os.environ[k] = v
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
-@contextlib.contextmanager
-def counted(gpu, mode):
-    """the switches of `mode` for the block; the dict it yields gets the block's tile launches, planned
-    launches and deferred steps"""
-    c = {}
-    with env(**MODES[mode]):
-        t0, p0, d0 = gpu.api.limb_tile_launches(), gpu.api.limb_tile_plan_launches(), gpu.api.limb_deferred()
-        yield c
-        c["tile_launches"] = gpu.api.limb_tile_launches() - t0
-        c["plan_launches"] = gpu.api.limb_tile_plan_launches() - p0
-        c["deferred"] = gpu.api.limb_deferred() - d0
-
-
-def run(gpu, model, params, mode, K=40, Hc=1, k0=0, dtype=None):
-    """K fused calls of Hc steps under `mode`: the outputs, the key and the counters"""
-    import torch
-
-    with counted(gpu, mode) as c:
-        b = gpu.DeviceBatch(model, params, n_t=20, k0=k0, horizon=K * Hc, outputs=OUTS, dtype=dtype)
-        b.key_steps = K * Hc
-        b.work_cot.zero_()
-        b.reset_best()
-        b.run_calls(K, call_horizon=Hc, best=True, accumulate=True)
-        torch.cuda.synchronize()
-        out = {k: getattr(b, k).cpu().numpy() for k in OUTS}
-        out["best_key"] = int(b.best_key.item())
-    out.update(c)
-    return out
-
-
-def same(a, b, what, outs=OUTS):
-    for k in outs:
-        assert np.array_equal(a[k], b[k], equal_nan=True), \
-            f"{what}: {k} differs on {int((a[k] != b[k]).sum())} entries (max {np.nanmax(np.abs(a[k].astype(float) - b[k].astype(float))):.3e})"
-    if "best_key" in a:
-        assert a["best_key"] == b["best_key"], what
+def run(gpu, model, params, mode, K=40, **kw):
+    """K fused calls of Hc steps under MODES[mode]: the outputs, the key and the counters"""
+    return kit.run(gpu, model, params, MODES[mode], K, **kw)
 
 
 def check_counters(r, what, default_planned=None):
@@ -172,26 +102,13 @@ def test_myant_deferred_steps(gpu, hmodels):
 
 def test_mixed_plan(gpu, hmodels):
     """myant + hexapod wavefronts on one sequence, planned for the launch's six limb lanes"""
-    import torch
     from hslabs_amd import synth
 
     params, idx = synth.gen_mixed(24)
     ms = [hmodels[n] for n in synth.MIXED_MODELS]
 
     def go(mode):
-        with counted(gpu, mode) as c:
-            mb = gpu.MixedBatch(ms, idx, params, n_t=20, k0=0, horizon=40, outputs=OUTS)
-            for k in ("tau", "cf"):
-                getattr(mb, k).fill_(float("nan"))
-            mb.key_steps = 40
-            mb.work_cot.zero_()
-            mb.reset_best()
-            mb.run_calls(40, call_horizon=1, best=True, accumulate=True)
-            torch.cuda.synchronize()
-            out = {k: getattr(mb, k).cpu().numpy() for k in OUTS}
-            out["best_key"] = int(mb.best_key.item())
-        out.update(c)
-        return out
+        return kit.run_mixed(gpu, ms, idx, params, MODES[mode], 40)
 
     r = {mode: go(mode) for mode in MODES}
     check_counters(r, "mixed", default_planned=1)
@@ -211,26 +128,14 @@ def test_second_chunk(gpu, hmodels):
 
 def test_forces_mode(gpu, hmodels):
     """solve_forces: contact forces and flags bitwise under every sequence"""
-    import torch
     from hslabs_amd import synth
 
     m, B, K = hmodels["hexapod"], 9, 40
     p = synth.gen_params(B, "hexapod", id0=11)
-    ctl = gpu.DeviceBatch(m, p, n_t=20, k0=0, horizon=K, outputs=("tau",))
-    ctl.run_calls(K, call_horizon=1)
-    i = torch.arange(K, device=ctl.tau.device)[None, :, None]
-    j = torch.arange(m.nmj, device=ctl.tau.device)[None, None, :]
-    tau = ctl.tau + 0.2 * torch.sin(0.7 * i + 1.3 * j)
+    tau = forces_tau(gpu, m, p, K)
 
     def go(mode):
-        with counted(gpu, mode) as c:
-            fb = gpu.DeviceBatch(m, p, n_t=20, k0=0, horizon=K, outputs=("cf", "flags"))
-            fb.cf.fill_(float("nan"))
-            fb.forces_launcher(tau, K, call_horizon=1)()
-            torch.cuda.synchronize()
-            out = dict(cf=fb.cf.cpu().numpy(), flags=fb.flags.cpu().numpy())
-        out.update(c)
-        return out
+        return kit.run_forces(gpu, m, p, tau, MODES[mode], K)
 
     r = {mode: go(mode) for mode in MODES}
     check_counters(r, "forces", default_planned=1)

@@ -1,9 +1,10 @@
-"""The tile descriptor of the limb-lane kernel's tile mapping (hslabs_amd/csrc/hs_limb_tile.h, limb_tile_desc_fill):
+"""The tile descriptor of the limb-lane kernel's tile mapping (hslabs_amd/csrc/hs_limb_tile.h, limb_tile_desc_build):
 per tile every slot's local step and table row, the request mask M and the requests in service order, built on
 the host from the launch's slot sequence and read by the TILE kernels in place of their per-lane derivation.
 
-The header is compiled into a small program (as test_limb_tile_plan.py does) that prints, per launch and for both
-the planner's sequence and the parity order, the descriptor as built. This test replays limb_tile_kd's rule in
+The header is compiled into a small program (as test_limb_tile_plan.py does) that prints, per launch and for the
+planner's sequence, the parity order and the forced chain order (limb_tile_desc_build's modes 1, 0 and 2), the
+sequence as the sequence functions give it and the descriptor as the launch's one entry builds it. This test replays limb_tile_kd's rule in
 Python on its own -- rows, sharing, requests, and which lane's FK provides which row in which pass -- and compares.
 The same program is built once more with -fsanitize=address,undefined and run over the same grid (host only)."""
 import itertools
@@ -19,7 +20,7 @@ S0S = [0, 256]
 CALLS = [(1, 0, 20), (1, 13, 20), (5, 0, 20), (3, 5, 20), (32, 0, 20), (1, 0, 21), (1, 0, 70)]  # (h, k0, n_t)
 LIMBS = [4, 6]
 CASES = list(itertools.product(NS, S0S, CALLS, LIMBS))
-SEQS = ["plan", "parity"]
+SEQS = ["plan", "parity", "chain"]  # limb_tile_desc_build's modes 1, 0 and 2
 
 PROG = r"""
 #include <cstdio>
@@ -31,13 +32,19 @@ int main(int argc, char** argv) {
     limb_tile_launch L;
     L.n = atoi(argv[i]), L.s0 = atoi(argv[i + 1]), L.h = atoi(argv[i + 2]), L.k0 = atoi(argv[i + 3]);
     L.n_t = atoi(argv[i + 4]), L.n_limbs = atoi(argv[i + 5]);
-    for (int seq = 0; seq < 2; seq++) {
+    const int modes[3] = {1, 0, 2};  // limb_tile_desc_build's mode of each sequence
+    for (int seq = 0; seq < 3; seq++) {
       int16_t step[HS_TILE_PLAN_STEPS];
-      if (seq == 0) limb_tile_plan(L, step);
-      else limb_tile_parity_fill(L.n, step);
+      int row[HS_TILE_PLAN_STEPS];
+      limb_tile_rows(L, row);
+      bool chain = seq == 2;
+      if (seq == 0) chain = limb_tile_plan(L, step);
+      else if (seq == 1) limb_tile_parity_fill(L.n, step);
+      else limb_tile_chain_fill(row, L.n, step);
       limb_tile_desc d;
       memset(&d, 0xee, sizeof d);
-      if (!limb_tile_desc_fill(L, step, d)) return 2;
+      bool planned = !chain;
+      if (!limb_tile_desc_build(L, modes[seq], d, &planned) || planned != chain) return 2;
       printf("%d %d %d %d %d %d %d  %d", L.n, L.s0, L.h, L.k0, L.n_t, L.n_limbs, seq, d.n_tiles);
       for (int s = 0; s < HS_TILE_SLOTS * limb_tile_count(L.n); s++) printf(" %d", step[s]);
       for (int t = 0; t < d.n_tiles; t++) {
@@ -96,7 +103,7 @@ def descs(tmp_path_factory):
         assert p == len(v)
         table[(n, s0, (h, k0, n_t), nl, SEQS[seq])] = dict(step=step, tiles=tiles)
     assert sorted(k[:4] for k in table if k[4] == "plan") == sorted(CASES)
-    assert len(table) == 2 * len(CASES)
+    assert len(table) == len(SEQS) * len(CASES)
     return table
 
 
@@ -191,6 +198,8 @@ def test_descriptor_equals_the_replay(descs, s0, call, nl, seq):
         slots = d["step"]
         if seq == "parity":
             assert slots == parity_order(n), n
+        if seq == "chain":  # every step of the launch once, the idle slots at the end
+            assert sorted(slots[:n]) == list(range(n)) and slots[n:] == [-1] * (8 * ((n + 7) // 8) - n), n
         assert len(d["tiles"]) == (n + 7) // 8, n
         for t, e in enumerate(d["tiles"]):
             tile = slots[8 * t:8 * t + 8]
@@ -232,11 +241,11 @@ def test_every_row_has_one_provider_of_the_right_row_and_pass(descs, s0, call, n
 
 
 def test_builder_under_sanitizers(tmp_path):
-    """limb_tile_desc_fill over the whole grid in a stand-alone program with -fsanitize=address,undefined"""
+    """limb_tile_desc_build over the whole grid in a stand-alone program with -fsanitize=address,undefined"""
     exe = _build(tmp_path, "desc_san", ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
     r = subprocess.run([str(exe), *ARGS], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
-    assert len(r.stdout.splitlines()) == 2 * len(CASES)
+    assert len(r.stdout.splitlines()) == len(SEQS) * len(CASES)
 
 
 def test_launches_a_descriptor_does_not_hold(tmp_path):
