@@ -643,6 +643,9 @@ class SimBatch:
         # the derivative tracker (configtimedertrack: zeros at construction) and the last motor torques
         self.ders = torch.zeros((self.B, 3, self.model.config_dim), dtype=torch.float64, device=self.device)
         self.last_tau = None
+        if getattr(self, "low_tpdist", None) is not None:  # the CPC controller's carried state (cpc.cpp:35, 42)
+            self.low_tpdist.fill_(1)
+            self.last_tpi.zero_()
 
     def step(self, n_steps: int = 1, stream=None, outputs=("tau_cmd", "q_meas", "torso", "n_contacts",
                                                            "normal_force")) -> dict:
@@ -868,6 +871,173 @@ class SimBatch:
         capi.check(capi.load().hs_sim_regress_B(self.model.handle, B, int(T.shape[1]), T.data_ptr(), U.data_ptr(),
                                                 res["Bt"].data_ptr(), res["rank"].data_ptr(), capi.HS_PREC_F64,
                                                 self._stream(stream)), "hs_sim_regress_B")
+        return res
+
+    # ---- configuration path control (cpccontroller, cpc.cpp; player.cpp:440-481)
+
+    @staticmethod
+    def cpc_default_params() -> "capi.CpcParamsC":
+        """The reference's live controller values (hs_cpc_default_params)."""
+        p = capi.CpcParamsC()
+        capi.load().hs_cpc_default_params(ctypes.byref(p))
+        return p
+
+    def cpc_target_points(self, mask=None, stream=None):
+        """cpccontroller::set_target_points_by_per (hs_cpc_target_points): [B][n_t][2 * config_dim + nmj],
+        row i = get_complete_traj_rec(i) from the batch's controller tables, masked (mask: a bit set,
+        default the reference's {0, 1, 5}). float64 batches only."""
+        torch = self.torch
+        _require(self.dtype == torch.float64, "CPC is float64 only")
+        cfg, nmj = self.model.config_dim, self.model.nmj
+        mask = self.cpc_default_params().mask if mask is None else int(mask)
+        tp = torch.empty((self.B, self.n_t, 2 * cfg + nmj), dtype=torch.float64, device=self.device)
+        capi.check(capi.load().hs_cpc_target_points(self.model.handle, self.B, self.n_t, self.tables.q.data_ptr(),
+                                                    self.tables.dq.data_ptr(), self.tables.tau.data_ptr(), mask,
+                                                    tp.data_ptr(), self._stream(stream)), "hs_cpc_target_points")
+        return tp
+
+    def _cpc_tp(self, tp):
+        """(tensor, n_tp, stride): tp [n_tp][rec] is one set shared by the batch (stride 0), [B][n_tp][rec] a
+        set per rollout; None = cpc_target_points(), built once"""
+        torch = self.torch
+        rec = 2 * self.model.config_dim + self.model.nmj
+        if tp is None:
+            if getattr(self, "_tp", None) is None:
+                self._tp = self.cpc_target_points()
+            tp = self._tp
+        tp = torch.as_tensor(tp, dtype=torch.float64, device=self.device).contiguous()
+        _require(tp.dim() in (2, 3) and tp.shape[-1] == rec and (tp.dim() == 2 or tp.shape[0] == self.B),
+                 "tp: [n_tp][2 * config_dim + nmj] or [B][n_tp][...]")
+        n_tp = int(tp.shape[-2])
+        return tp, n_tp, (0 if tp.dim() == 2 else n_tp * rec)
+
+    def _cpc_state(self):
+        torch = self.torch
+        if getattr(self, "low_tpdist", None) is None:
+            self.low_tpdist = torch.ones((self.B,), dtype=torch.int32, device=self.device)  # cpc.cpp:42
+            self.last_tpi = torch.zeros((self.B,), dtype=torch.int32, device=self.device)
+            self.cpc_flags = torch.zeros((self.B,), dtype=torch.int32, device=self.device)
+
+    def cpc_torques(self, Bt, tp=None, params=None, state=None, stream=None, **diagnostics) -> dict:
+        """cpccontroller::get_motor_torques per rollout (hs_cpc_torques) on Bt [B][nmj][config_dim] and the
+        tracker's (q, dq) = ``self.ders[:, 0]``, ``self.ders[:, 1]`` (``state``: another [B][>= 2][config_dim]
+        tensor). tp as cpc_target_points() (default), [n_tp][...] shared or [B][n_tp][...]; params a
+        CpcParamsC (default cpc_default_params()). Reads and advances ``self.low_tpdist`` (starts 1), sets
+        ``self.last_tpi``. Returns ``tau`` [B][nmj], ``last_tpi``, ``flags``, ``low_tpdist`` and the
+        diagnostics named as keywords (``loss=True`` [B][n_tp], ``cand_tpi`` [B][n_cand], ``cand_t0s``
+        [B][n_cand][2], ``passes`` [B], ``i_best`` [B])."""
+        torch = self.torch
+        _require(self.dtype == torch.float64, "CPC is float64 only")
+        B, nmj, cfg = self.B, self.model.nmj, self.model.config_dim
+        P = self.cpc_default_params() if params is None else params
+        Bt = torch.as_tensor(Bt, dtype=torch.float64, device=self.device).contiguous()
+        _require(tuple(Bt.shape) == (B, nmj, cfg), "Bt: [B][nmj][config_dim]")
+        state = self.ders if state is None else state
+        _require(state.dim() == 3 and state.shape[0] == B and state.shape[1] >= 2 and state.shape[2] == cfg and
+                 state.is_contiguous() and state.dtype == torch.float64, "state: [B][>= 2][config_dim] float64")
+        tp, n_tp, tp_stride = self._cpc_tp(tp)
+        self._cpc_state()
+        i32 = dict(dtype=torch.int32, device=self.device)
+        f64 = dict(dtype=torch.float64, device=self.device)
+        nc = int(P.n_cand)
+        shapes = {"loss": ((B, n_tp), f64), "cand_tpi": ((B, max(nc, 0)), i32), "cand_t0s": ((B, max(nc, 0), 2), f64),
+                  "passes": ((B,), i32), "i_best": ((B,), i32)}
+        res = {"tau": torch.empty((B, nmj), **f64)}
+        for k, v in diagnostics.items():
+            if k not in shapes:
+                raise TypeError(f"unknown diagnostic {k}")
+            if v:
+                res[k] = torch.empty(shapes[k][0], **shapes[k][1])
+        a = capi.CpcArgsC()
+        a.n_rollouts, a.n_tp, a.precision, a.params = B, n_tp, self.precision, P
+        a.Bt, a.state, a.state_stride = Bt.data_ptr(), state.data_ptr(), int(state.shape[1]) * cfg
+        a.tp, a.tp_stride = tp.data_ptr(), tp_stride
+        a.low_tpdist, a.tau = self.low_tpdist.data_ptr(), res["tau"].data_ptr()
+        a.last_tpi, a.flags = self.last_tpi.data_ptr(), self.cpc_flags.data_ptr()
+        for k in shapes:
+            setattr(a, k, res[k].data_ptr() if k in res else None)
+        a.stream = self._stream(stream)
+        capi.check(capi.load().hs_cpc_torques(self.model.handle, ctypes.byref(a)), "hs_cpc_torques")
+        res.update(last_tpi=self.last_tpi, flags=self.cpc_flags, low_tpdist=self.low_tpdist)
+        return res
+
+    def cpc_step(self, n_steps: int, dtau=None, seed: int = 0, tp=None, params=None, m=None, *,
+                 torque_limit: float = 0.0, kick_every: int = 0, kick_phase: int | None = None, kick_dv=None,
+                 hc: float = 0.0, check_from: int = 0, check_until: int = -1, stream=None, **outputs) -> dict:
+        """n_steps of simulate_ode with cpc_control_flag and dynamics_from_simulation_flag (hs_sim_cpc_step),
+        enqueued without a host synchronisation: per step estimate_B (around the last torques applied),
+        cpc_torques on the tracker, one open-loop trial step with the CPC torques (torque limit, kicks and
+        fall check as trial()). dtau [n_steps][B][m][nmj] or [B][m][nmj] (one set for every step); default
+        synth.gen_torque_perturbations(n_steps * B, m, nmj, seed=seed) with m = config_dim + 20. Owns
+        ``self.low_tpdist``, ``self.last_tpi``, ``self.cpc_flags`` and the trial state; ``self.last_tau``
+        is read (zeros before any step) and advanced. A frozen rollout keeps body, seed, tsi, its
+        last_tau row and its output rows; the estimate and the controller still run on it. The reference's
+        first two steps are position control (player.cpp:468): call estimate_B() + step(1) twice first.
+        Outputs named as keywords are STEP-major: ``tau_cmd`` / ``q_meas`` [n_steps][B][nmj], ``torso``
+        [n_steps][B][3], ``n_contacts`` / ``normal_force`` [n_steps][B] (rows not reached keep NaN / -1)."""
+        from . import synth
+        torch = self.torch
+        _require(self.dtype == torch.float64, "CPC is float64 only")
+        B, nmj, cfg = self.B, self.model.nmj, self.model.config_dim
+        P = self.cpc_default_params() if params is None else params
+        if dtau is None:
+            m = cfg + 20 if m is None else int(m)
+            dtau = synth.gen_torque_perturbations(n_steps * B, m, nmj, seed=seed).reshape(n_steps, B, m, nmj)
+        dtau = torch.as_tensor(dtau, dtype=torch.float64, device=self.device).contiguous()
+        _require(dtau.dim() in (3, 4) and tuple(dtau.shape[-3::2]) == (B, nmj) and
+                 (dtau.dim() == 3 or dtau.shape[0] == n_steps), "dtau: [n_steps][B][m][nmj] or [B][m][nmj]")
+        m = int(dtau.shape[-2])
+        tp, n_tp, tp_stride = self._cpc_tp(tp)
+        self._cpc_state()
+        if not hasattr(self, "state"):
+            self.state = torch.full((B,), capi.HS_TRIAL_RUNNING, dtype=torch.int32, device=self.device)
+            self.fall_z = torch.full((B,), float("nan"), dtype=self.dtype, device=self.device)
+        tau0 = self._tau0(None)
+        tau0 = torch.zeros((B, nmj), dtype=torch.float64, device=self.device) if tau0 is None else tau0.clone()
+        shapes = {"tau_cmd": (n_steps, B, nmj), "q_meas": (n_steps, B, nmj), "torso": (n_steps, B, 3),
+                  "n_contacts": (n_steps, B), "normal_force": (n_steps, B)}
+        res = {}
+        for k, v in outputs.items():
+            if k not in shapes:
+                raise TypeError(f"unknown output {k}")
+            if v:
+                res[k] = torch.full(shapes[k], -1, dtype=torch.int32, device=self.device) if k == "n_contacts" else \
+                    torch.full(shapes[k], float("nan"), dtype=torch.float64, device=self.device)
+        L = capi.load()
+        c = capi.SimCpcArgsC()
+        t = c.trial
+        a = t.sim
+        a.n_rollouts, a.n_steps, a.n_t, a.precision, a.params = B, int(n_steps), 1, self.precision, self.params
+        a.body, a.seed, a.tsi = self.body.data_ptr(), self.seed.data_ptr(), self.tsi.data_ptr()
+        for k in shapes:
+            setattr(a, k, res[k].data_ptr() if k in res else None)
+        a.stream = self._stream(stream)
+        t.open_loop = 1
+        t.torque_limit = float(torque_limit)
+        t.kick_every = int(kick_every)
+        t.kick_phase = int(kick_every) - 1 if kick_phase is None else int(kick_phase)
+        if kick_dv is not None:
+            dv = torch.as_tensor(kick_dv, dtype=self.dtype, device=self.device).contiguous()
+            _require(tuple(dv.shape) == (B, 3), "kick_dv: [B][3]")
+            self._kick_dv = dv
+            t.kick_dv = dv.data_ptr()
+        t.hc = float(hc)
+        t.check_from, t.check_until = int(check_from), int(check_until)
+        t.state, t.fall_z = self.state.data_ptr(), self.fall_z.data_ptr()
+        c.cpc, c.m, c.n_tp = P, m, n_tp
+        c.dtau, c.dtau_step_stride = dtau.data_ptr(), (B * m * nmj if dtau.dim() == 4 else 0)
+        c.tp, c.tp_stride = tp.data_ptr(), tp_stride
+        rank = torch.empty((B,), dtype=torch.int32, device=self.device)
+        c.ders, c.tau0 = self.ders.data_ptr(), tau0.data_ptr()
+        c.low_tpdist, c.last_tpi = self.low_tpdist.data_ptr(), self.last_tpi.data_ptr()
+        c.flags, c.rank = self.cpc_flags.data_ptr(), rank.data_ptr()
+        nbytes = int(L.hs_sim_cpc_workspace(self.model.handle, B, m))
+        ws = torch.empty(((nbytes + 7) // 8,), dtype=torch.float64, device=self.device)
+        c.workspace, c.workspace_bytes = ws.data_ptr(), ws.numel() * 8
+        capi.check(L.hs_sim_cpc_step(self.model.handle, ctypes.byref(c)), "hs_sim_cpc_step")
+        self.last_tau = tau0
+        res.update(state=self.state, fall_z=self.fall_z, last_tpi=self.last_tpi, flags=self.cpc_flags,
+                   low_tpdist=self.low_tpdist, rank=rank, last_tau=tau0)
         return res
 
     def traj_record(self):

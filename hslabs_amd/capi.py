@@ -41,6 +41,7 @@ EXPORTS = [
     "hs_sim_default_params", "hs_sim_reset", "hs_sim_step", "hs_sim_create", "hs_sim_advance", "hs_sim_get_state",
     "hs_sim_free", "hs_sim_trial", "hs_sim_trial_summary", "hs_sim_set_trial", "hs_sim_get_trial_state",
     "hs_sim_config", "hs_sim_track_push", "hs_sim_probe", "hs_sim_estimate_workspace",
+    "hs_cpc_default_params", "hs_cpc_torques", "hs_cpc_target_points", "hs_sim_cpc_workspace", "hs_sim_cpc_step",
     "hs_batch_create", "hs_batch_set_params", "hs_batch_run", "hs_batch_run_device", "hs_select_best",
     "hs_batch_best_key_device", "hs_batch_free", "hs_comm_unique_id", "hs_comm_init", "hs_comm_free", "hs_comm_size",
     "hs_comm_reduce_best", "hs_select_best_comm", "hs_pergen_rec", "hs_pergen_rec_host", "hs_model_lik",
@@ -56,6 +57,9 @@ HS_FLAG_LIK_FAILED = 128
 SIM_BODY_STRIDE = 13
 HS_TRIAL_RUNNING = -1
 HS_TRIAL_SURVIVED = -2
+HS_CPC_FLAG_NONFINITE = 1  # a target point's loss was not finite; it sorted last (include/hslabs.h)
+HS_CPC_FLAG_NOSCORE = 2    # no candidate had a finite score; i_best = 0
+HS_CPC_FLAG_RANK = 4       # Bt_chi or B_chi rank deficient; Eigen's basic solution
 
 
 class GaitParamsC(ctypes.Structure):
@@ -156,6 +160,32 @@ class SimEstimateArgsC(ctypes.Structure):
     """hs_sim_estimate_args."""
     _fields_ = [("probe", SimProbeArgsC)] + \
                [(f, ctypes.c_void_p) for f in ("ders", "U", "Bt", "rank", "workspace")] + \
+               [("workspace_bytes", ctypes.c_size_t)]
+
+
+class CpcParamsC(ctypes.Structure):
+    """hs_cpc_params."""
+    _fields_ = [(f, ctypes.c_double) for f in ("w", "sg", "k0", "kc", "tauc", "loss_cc", "tp_dist")] + \
+               [("n_cand", ctypes.c_int32), ("goal_t0s", ctypes.c_int32), ("tpdist_switch", ctypes.c_int32),
+                ("mask", ctypes.c_uint32)]
+
+
+class CpcArgsC(ctypes.Structure):
+    """hs_cpc_args."""
+    _fields_ = [("n_rollouts", ctypes.c_int32), ("n_tp", ctypes.c_int32), ("precision", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("params", CpcParamsC), ("Bt", ctypes.c_void_p),
+                ("state", ctypes.c_void_p), ("state_stride", ctypes.c_int64), ("tp", ctypes.c_void_p),
+                ("tp_stride", ctypes.c_int64)] + \
+               [(f, ctypes.c_void_p) for f in ("low_tpdist", "tau", "last_tpi", "flags", "loss", "cand_tpi", "cand_t0s",
+                                               "passes", "i_best", "stream")]
+
+
+class SimCpcArgsC(ctypes.Structure):
+    """hs_sim_cpc_args."""
+    _fields_ = [("trial", SimTrialArgsC), ("cpc", CpcParamsC), ("m", ctypes.c_int32), ("n_tp", ctypes.c_int32),
+                ("dtau", ctypes.c_void_p), ("dtau_step_stride", ctypes.c_int64), ("tp", ctypes.c_void_p),
+                ("tp_stride", ctypes.c_int64)] + \
+               [(f, ctypes.c_void_p) for f in ("ders", "tau0", "low_tpdist", "last_tpi", "flags", "rank", "workspace")] + \
                [("workspace_bytes", ctypes.c_size_t)]
 
 
@@ -270,6 +300,13 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
     L.hs_sim_estimate_workspace.argtypes = [vp, ctypes.c_int32, ctypes.c_int32]
     L.hs_sim_estimate_workspace.restype = ctypes.c_size_t
     L.hs_sim_estimate_B.argtypes = [vp, ctypes.POINTER(SimEstimateArgsC)]
+    L.hs_cpc_default_params.argtypes = [ctypes.POINTER(CpcParamsC)]
+    L.hs_cpc_default_params.restype = None
+    L.hs_cpc_torques.argtypes = [vp, ctypes.POINTER(CpcArgsC)]
+    L.hs_cpc_target_points.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, ctypes.c_uint32, vp, vp]
+    L.hs_sim_cpc_workspace.argtypes = [vp, ctypes.c_int32, ctypes.c_int32]
+    L.hs_sim_cpc_workspace.restype = ctypes.c_size_t
+    L.hs_sim_cpc_step.argtypes = [vp, ctypes.POINTER(SimCpcArgsC)]
     L.hs_batch_create.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint32,
                                   ctypes.POINTER(vp)]
     L.hs_batch_set_params.argtypes = [vp, ctypes.POINTER(GaitParamsC)]

@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cfloat>
 #include <cstring>
 #include <fstream>
 #include <mutex>
@@ -1630,6 +1631,199 @@ int hs_sim_estimate_B(hs_model_t m, const hs_sim_estimate_args* t) {
     if (e != 0) return hip_fail((hipError_t)e, "hs_sim_estimate_B launch");
   }
   return hs_sim_regress_B(m, a->n_rollouts, a->m, a->tau_out, t->U, t->Bt, t->rank, HS_PREC_F64, a->stream);
+}
+
+// ---- configuration path control (hs_cpc.hip); every check comes before the first device call
+
+void hs_cpc_default_params(hs_cpc_params* p) {
+  if (!p) return;
+  memset(p, 0, sizeof(*p));
+  // set_w_sg_nd_k0_kc_tauc(10, 1, 10, 100*2, 10, 20) (player.cpp:453)
+  p->w = 10;
+  p->sg = 1;
+  p->n_cand = 10;
+  p->k0 = 200;
+  p->kc = 10;
+  p->tauc = 20;
+  p->loss_cc = 10;    // cpc.cpp:188
+  p->tp_dist = 0.5;   // cpc.cpp:490
+  p->goal_t0s = 1;    // player.cpp:458, which switches tpdist_switch on (cpc.cpp:451)
+  p->tpdist_switch = 1;
+  p->mask = (1u << 0) | (1u << 1) | (1u << 5);  // cpc.cpp:40-41
+}
+
+// the checks of hs_cpc_torques, apart from its pointers (hs_sim_cpc_step fills those in itself)
+static int cpc_check(hs_model_t m, int32_t n, int32_t n_tp, int32_t precision, const hs_cpc_params& P) {
+  if (!m) return fail(HS_E_ARG, "null model");
+  if (n < 0 || n > (1 << 30)) return fail(HS_E_ARG, "bad n_rollouts");
+  if (precision != HS_PREC_F64) return fail(HS_E_ARG, "the CPC controller is double precision only");
+  if (P.n_cand < 1 || P.n_cand > 64) return fail(HS_E_ARG, "n_cand must lie in 1..64");
+  if (n_tp < P.n_cand) return fail(HS_E_ARG, "n_tp < n_cand");
+  // the gain loop halves k until k <= kc: it ends for a finite k0 and kc > 0 only
+  if (!(P.k0 <= DBL_MAX) || !(P.kc > 0)) return fail(HS_E_ARG, "k0 must be finite and kc > 0 (the gain loop would not end)");
+  const int cfg = m->host.cfg, nmj = m->sim.nmj;
+  if (cfg > 32 || nmj < 1 || nmj >= cfg) return fail(HS_E_TOPOLOGY, "model outside the CPC kernel's sizes");
+  if (hs::cpc_lds_bytes(n_tp, P.n_cand, nmj, cfg) > 64 * 1024)
+    return fail(HS_E_ARG, "n_tp too large for the CPC kernel (64 KB of LDS)");
+  return HS_OK;
+}
+
+int hs_cpc_torques(hs_model_t m, const hs_cpc_args* a) {
+  if (!m || !a) return fail(HS_E_ARG, "null model or args");
+  int rc = cpc_check(m, a->n_rollouts, a->n_tp, a->precision, a->params);
+  if (rc != HS_OK) return rc;
+  if (a->state_stride < 2 * (int64_t)m->host.cfg) return fail(HS_E_ARG, "state_stride < 2 * config_dim");
+  if (a->tp_stride != 0 && a->tp_stride < (int64_t)a->n_tp * (2 * m->host.cfg + m->sim.nmj))
+    return fail(HS_E_ARG, "tp_stride smaller than one set of target points (0: a shared set)");
+  if (a->n_rollouts == 0) return HS_OK;
+  if (!a->Bt || !a->state || !a->tp || !a->low_tpdist || !a->tau || !a->last_tpi || !a->flags)
+    return fail(HS_E_ARG, "Bt, state, tp, low_tpdist, tau, last_tpi and flags are required");
+  int e = hs::launch_cpc_torques(*a, m->sim.nmj, m->host.cfg);
+  if (e != 0) return hip_fail((hipError_t)e, "hs_cpc_torques launch");
+  return HS_OK;
+}
+
+int hs_cpc_target_points(hs_model_t m, int32_t n, int32_t n_t, const double* q_tab, const double* dq_tab,
+                         const double* tau_tab, uint32_t mask, double* tp, void* stream) {
+  if (!m) return fail(HS_E_ARG, "null model");
+  if (n < 0 || n > (1 << 30)) return fail(HS_E_ARG, "bad n_rollouts");
+  if (n_t < 1) return fail(HS_E_ARG, "n_t must be >= 1");
+  if (n == 0) return HS_OK;
+  if (!q_tab || !dq_tab || !tau_tab || !tp) return fail(HS_E_ARG, "null table or tp");
+  int e = hs::launch_cpc_target_points(n, n_t, m->host.cfg, m->sim.nmj, q_tab, dq_tab, tau_tab, mask, tp, stream);
+  if (e != 0) return hip_fail((hipError_t)e, "hs_cpc_target_points launch");
+  return HS_OK;
+}
+
+// the workspace of hs_sim_cpc_step, in doubles: config_out, T, U, Bt, the CPC torques, a copy of the seeds,
+// then the estimate's own
+struct cpc_ws {
+  size_t config_out, T, U, Bt, tau, seed, est, total_bytes;
+  cpc_ws(hs_model_t m, int32_t B, int32_t ms) {
+    const size_t cfg = m->host.cfg, nmj = m->sim.nmj, n = B, mm = ms;
+    size_t o = 0;
+    config_out = o; o += n * mm * cfg;
+    T = o; o += n * mm * nmj;
+    U = o; o += n * mm * cfg;
+    Bt = o; o += n * nmj * cfg;
+    tau = o; o += n * nmj;
+    seed = o; o += (n + 1) / 2;  // uint32 [B]: the seeds before the estimate
+    est = o;
+    total_bytes = o * sizeof(double) + ((hs_sim_estimate_workspace(m, B, ms) + 7) & ~(size_t)7);
+  }
+};
+
+size_t hs_sim_cpc_workspace(hs_model_t m, int32_t n_rollouts, int32_t ms) {
+  if (!m || n_rollouts <= 0 || ms < 0) return 0;
+  return cpc_ws(m, n_rollouts, ms).total_bytes;
+}
+
+int hs_sim_cpc_step(hs_model_t m, const hs_sim_cpc_args* c) {
+  if (!m || !c) return fail(HS_E_ARG, "null model or args");
+  const hs_sim_args& s = c->trial.sim;
+  const int32_t B = s.n_rollouts;
+  // the three parts' arguments, checked by the parts' own rules before anything is enqueued
+  hs_sim_estimate_args est;
+  memset(&est, 0, sizeof(est));
+  hs_sim_probe_args& pr = est.probe;
+  pr.n_rollouts = B;
+  pr.m = c->m;
+  pr.precision = s.precision;
+  pr.params = s.params;
+  pr.body = s.body;
+  pr.seed = s.seed;
+  pr.stream = s.stream;
+  bool nothing = false;
+  pr.dtau = c->dtau;
+  if (!c->workspace) return fail(HS_E_ARG, "workspace missing");
+  pr.config_out = pr.tau_out = (double*)c->workspace;  // both lie in the workspace; placed once its size is checked
+  int rc = probe_args_check(m, &pr, &nothing);
+  if (rc != HS_OK) return rc;
+  rc = regress_check(m, B, c->m, s.precision);
+  if (rc != HS_OK) return rc;
+  rc = cpc_check(m, B, c->n_tp, s.precision, c->cpc);
+  if (rc != HS_OK) return rc;
+  if (c->tp_stride != 0 && c->tp_stride < (int64_t)c->n_tp * (2 * m->host.cfg + m->sim.nmj))
+    return fail(HS_E_ARG, "tp_stride smaller than one set of target points (0: a shared set)");
+  if (c->dtau_step_stride != 0 && c->dtau_step_stride < (int64_t)B * c->m * m->sim.nmj)
+    return fail(HS_E_ARG, "dtau_step_stride smaller than one step's perturbations (0: one set)");
+  hs_sim_trial_args tr = c->trial;
+  tr.sim.n_steps = 1;
+  tr.sim.n_t = 1;
+  tr.sim.params.k = 0;  // open loop applies the table row whatever k is; k = 0 needs no q / dq tables
+  tr.sim.q_tab = tr.sim.dq_tab = nullptr;
+  tr.sim.tau_tab = (const double*)c->workspace;  // placeholder
+  tr.open_loop = 1;
+  if (s.n_steps < 0) return fail(HS_E_ARG, "n_steps < 0");
+  {
+    hs_sim_trial_args chk = tr;
+    chk.sim.n_rollouts = chk.sim.n_steps = 0;  // the parameter checks alone
+    if (B > 0 && (!s.body || !s.seed || !s.tsi)) return fail(HS_E_ARG, "body, seed and tsi are required");
+    rc = hs_sim_trial(m, &chk);
+    if (rc != HS_OK) return rc;
+  }
+  if (B == 0 || s.n_steps == 0) return HS_OK;
+  if (!c->trial.state) return fail(HS_E_ARG, "the trial state array is required");
+  if (!c->tp || !c->ders || !c->tau0 || !c->low_tpdist || !c->last_tpi || !c->flags || !c->rank || (c->m > 0 && !c->dtau))
+    return fail(HS_E_ARG, "dtau, tp, ders, tau0, low_tpdist, last_tpi, flags and rank are required");
+  const cpc_ws W(m, B, c->m);
+  if (c->workspace_bytes < W.total_bytes) return fail(HS_E_ARG, "workspace smaller than hs_sim_cpc_workspace");
+  double* ws = (double*)c->workspace;
+  const size_t nmj = m->sim.nmj;
+  pr.tau0 = c->tau0;
+  pr.config_out = ws + W.config_out;
+  pr.tau_out = ws + W.T;
+  est.ders = c->ders;
+  est.U = ws + W.U;
+  est.Bt = ws + W.Bt;
+  est.rank = c->rank;
+  est.workspace = ws + W.est;
+  est.workspace_bytes = hs_sim_estimate_workspace(m, B, c->m);
+  hs_cpc_args ca;
+  memset(&ca, 0, sizeof(ca));
+  ca.n_rollouts = B;
+  ca.n_tp = c->n_tp;
+  ca.precision = HS_PREC_F64;
+  ca.params = c->cpc;
+  ca.Bt = est.Bt;
+  ca.state = c->ders;
+  ca.state_stride = 3 * (int64_t)m->host.cfg;
+  ca.tp = c->tp;
+  ca.tp_stride = c->tp_stride;
+  ca.low_tpdist = c->low_tpdist;
+  ca.tau = ws + W.tau;
+  ca.last_tpi = c->last_tpi;
+  ca.flags = c->flags;
+  ca.stream = s.stream;
+  tr.sim.tau_tab = ca.tau;  // [B][1][nmj]: the one-row table
+  for (int32_t k = 0; k < s.n_steps; k++) {
+    pr.dtau = c->dtau + (size_t)k * c->dtau_step_stride;
+    // a rollout frozen before this step keeps its seed: the estimate runs on the whole batch, so the seeds
+    // are saved and a frozen rollout's is put back
+    uint32_t* seed0 = (uint32_t*)(ws + W.seed);
+    hipError_t he = hipMemcpyAsync(seed0, s.seed, (size_t)B * sizeof(uint32_t), hipMemcpyDeviceToDevice,
+                                   (hipStream_t)s.stream);
+    if (he != hipSuccess) return hip_fail(he, "hs_sim_cpc_step seed copy");
+    rc = hs_sim_estimate_B(m, &est);
+    if (rc != HS_OK) return rc;
+    int se = hs::launch_cpc_keep_seed(B, tr.state, seed0, s.seed, s.stream);
+    if (se != 0) return hip_fail((hipError_t)se, "hs_sim_cpc_step launch");
+    rc = hs_cpc_torques(m, &ca);
+    if (rc != HS_OK) return rc;
+    // the torques applied go to tau0 (a frozen rollout's row stays), then to the caller's row of this step
+    tr.sim.tau_cmd = c->tau0;
+    tr.sim.q_meas = s.q_meas ? s.q_meas + (size_t)k * B * nmj : nullptr;
+    tr.sim.torso = s.torso ? s.torso + (size_t)k * B * 3 : nullptr;
+    tr.sim.n_contacts = s.n_contacts ? s.n_contacts + (size_t)k * B : nullptr;
+    tr.sim.normal_force = s.normal_force ? s.normal_force + (size_t)k * B : nullptr;
+    rc = hs_sim_trial(m, &tr);
+    if (rc != HS_OK) return rc;
+    if (s.tau_cmd) {
+      int e = hs::launch_cpc_rows(B, (int32_t)nmj, tr.state, c->tau0, s.tau_cmd + (size_t)k * B * nmj, s.stream);
+      if (e != 0) return hip_fail((hipError_t)e, "hs_sim_cpc_step launch");
+    }
+  }
+  return HS_OK;
 }
 
 struct hs_sim_s {

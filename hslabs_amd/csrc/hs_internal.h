@@ -184,6 +184,16 @@ int launch_probe_accel(int32_t n, int32_t m, int32_t cfg, const double* config_o
 int launch_regress_B(int32_t n, int32_t m, int32_t nmj, int32_t cfg, const double* T, const double* U, double* Bt,
                      int32_t* rank, void* stream);
 size_t regress_lds_bytes(int32_t m, int32_t nmj, int32_t cfg);
+// configuration path control (hs_cpc.hip): the controller (one wavefront per rollout; cpc_lds_bytes: its
+// LDS, the caller rejects more than 64 KB), set_target_points_by_per from the controller tables, and
+// dst[b] = src[b] for the rollouts whose trial state is still HS_TRIAL_RUNNING (hs_sim_cpc_step's outputs)
+size_t cpc_lds_bytes(int32_t n_tp, int32_t n_cand, int32_t nmj, int32_t cfg);
+int launch_cpc_torques(const hs_cpc_args& a, int32_t nmj, int32_t cfg);
+int launch_cpc_target_points(int32_t n, int32_t n_t, int32_t cfg, int32_t nmj, const double* q_tab, const double* dq_tab,
+                             const double* tau_tab, uint32_t mask, double* tp, void* stream);
+int launch_cpc_rows(int32_t n, int32_t width, const int32_t* state, const double* src, double* dst, void* stream);
+// seed[b] = saved[b] for the rollouts whose trial state is not HS_TRIAL_RUNNING
+int launch_cpc_keep_seed(int32_t n, const int32_t* state, const uint32_t* saved, uint32_t* seed, void* stream);
 
 }  // namespace hs
 

@@ -9,6 +9,8 @@
 
 #include <cfloat>
 
+#include "hs_colpiv.h"
+
 namespace {
 
 // visualizer::get_ode_config (visualization.cpp:378-396), one lane per rollout: torso pose, then
@@ -68,13 +70,10 @@ __global__ __launch_bounds__(256) void hs_probe_accel_kernel(int32_t n_rollouts,
 }
 
 // B_from_T_U (player.cpp:531-546), one wavefront per rollout, everything in LDS: A = [T^T | 1]
-// (m x (nmj + 1), column-major), Eigen 3.3 ColPivHouseholderQR of it -- the column-norm downdate, the
-// nonzero-pivot rule and the solve as hs_kernels.hip's colpiv_qr / qr_solve restate them for the square
-// systems of the contact solve; this one is rectangular, sized at run time and unfused, so it is restated
-// here -- then B.row(i) = solve(U.row(i)^T), one lane per right-hand side i, and Bt[j] = B.col(j) for
-// j < nmj (the constant column is dropped). rank = Eigen's nonzeroPivots(), the count its solve uses.
-// Pivot search and Householder norm run on every lane over LDS broadcasts (wave-uniform loops): no
-// single-lane loop, the shape tools/isa_check.py guards against.
+// (m x (nmj + 1), column-major), Eigen 3.3 ColPivHouseholderQR of it (hs_colpiv.h, shared with the
+// configuration path controller), then B.row(i) = solve(U.row(i)^T), one lane per right-hand side i, and
+// Bt[j] = B.col(j) for j < nmj (the constant column is dropped). rank = Eigen's nonzeroPivots(), the
+// count its solve uses.
 __global__ __launch_bounds__(WAVE) void hs_regress_kernel(int32_t n_rollouts, int32_t m, int32_t nmj, int32_t cfg,
                                                            const double* __restrict__ Tg, const double* __restrict__ Ug,
                                                            double* __restrict__ Bt, int32_t* __restrict__ rank) {
@@ -99,116 +98,10 @@ __global__ __launch_bounds__(WAVE) void hs_regress_kernel(int32_t n_rollouts, in
   for (int e = lane; e < m * nmj; e += WAVE) qr[e / nmj + (e % nmj) * m] = Tb[e];
   for (int r = lane; r < m; r += WAVE) qr[r + nmj * m] = 1.0;
   for (int e = lane; e < m * cfg; e += WAVE) C[e] = Ub[e];
-  if (lane < n) perm[lane] = lane;
-  wave_sync();
-  if (lane < n) {
-    double s = 0;
-    for (int i = 0; i < m; i++) s += qr[i + lane * m] * qr[i + lane * m];
-    nd[lane] = sqrt(s);
-    nu[lane] = nd[lane];
-  }
-  wave_sync();
-  double mx = 0;
-  for (int j = 0; j < n; j++) mx = fmax(mx, nu[j]);
-  const double th = mx * DBL_EPSILON;
-  const double threshold_helper = th * th / (double)m;
-  const double ndt = sqrt(DBL_EPSILON);
-  int np = n;
-  for (int p = 0; p < n; p++) {
-    int bi = p;
-    double bv = nu[p];
-    for (int j = p + 1; j < n; j++)
-      if (nu[j] > bv) { bv = nu[j]; bi = j; }
-    bi = __builtin_amdgcn_readfirstlane(bi);
-    if (np == n && bv * bv < threshold_helper * (double)(m - p)) np = p;
-    wave_sync();
-    if (bi != p) {
-      for (int r = lane; r < m; r += WAVE) {
-        const double t = qr[r + p * m];
-        qr[r + p * m] = qr[r + bi * m];
-        qr[r + bi * m] = t;
-      }
-      if (lane == 0) {
-        double t = nu[p]; nu[p] = nu[bi]; nu[bi] = t;
-        t = nd[p]; nd[p] = nd[bi]; nd[bi] = t;
-        const int ti = perm[p]; perm[p] = perm[bi]; perm[bi] = ti;
-      }
-    }
-    wave_sync();
-    // makeHouseholderInPlace on column p, rows p..m-1
-    const int len = m - p;
-    const double c0 = qr[p + p * m];
-    double tail = 0;
-    for (int i = 1; i < len; i++) tail += qr[p + i + p * m] * qr[p + i + p * m];
-    double tau, beta;
-    if (len == 1 || tail <= DBL_MIN) {
-      tau = 0;
-      beta = c0;
-      for (int i = 1 + lane; i < len; i += WAVE) qr[p + i + p * m] = 0;
-    } else {
-      beta = sqrt(c0 * c0 + tail);
-      if (c0 >= 0) beta = -beta;
-      const double den = c0 - beta;
-      for (int i = 1 + lane; i < len; i += WAVE) qr[p + i + p * m] /= den;
-      tau = (beta - c0) / beta;
-    }
-    wave_sync();
-    if (lane == 0) { qr[p + p * m] = beta; hc[p] = tau; }
-    // apply to columns p+1..n-1, then downdate their norms (one column per lane)
-    const int j = lane;
-    if (j > p && j < n) {
-      if (len == 1) {
-        qr[p + j * m] *= (1 - tau);
-      } else if (tau != 0) {
-        double tmp = 0;
-        for (int i = 1; i < len; i++) tmp += qr[p + i + p * m] * qr[p + i + j * m];
-        tmp += qr[p + j * m];
-        qr[p + j * m] -= tau * tmp;
-        for (int i = 1; i < len; i++) qr[p + i + j * m] -= tau * qr[p + i + p * m] * tmp;
-      }
-      if (nu[j] != 0) {
-        double temp = fabs(qr[p + j * m]) / nu[j];
-        temp = (1 + temp) * (1 - temp);
-        temp = temp < 0 ? 0 : temp;
-        const double ratio = nu[j] / nd[j];
-        const double temp2 = temp * (ratio * ratio);
-        if (temp2 <= ndt) {
-          double s = 0;
-          for (int i = p + 1; i < m; i++) s += qr[i + j * m] * qr[i + j * m];
-          nd[j] = sqrt(s);
-          nu[j] = nd[j];
-        } else {
-          nu[j] *= sqrt(temp);
-        }
-      }
-    }
-    wave_sync();
-  }
-  np = __builtin_amdgcn_readfirstlane(np);
-  // solve: c = Q^T u (the first np reflections), R z = c, B.row(i)[perm[k]] = z[k]; lane = right-hand side
+  const int np = hs_colpiv::factor(qr, m, n, nu, nd, hc, perm, lane);
+  // B.row(i)[perm[k]] = z[k]; lane = right-hand side
   const int i = lane;
-  for (int p = 0; p < np; p++) {
-    const int len = m - p;
-    const double tau = hc[p];
-    if (i < cfg) {
-      if (len == 1) {
-        C[p * cfg + i] *= (1 - tau);
-      } else if (tau != 0) {
-        double tmp = 0;
-        for (int r = 1; r < len; r++) tmp += qr[p + r + p * m] * C[(p + r) * cfg + i];
-        tmp += C[p * cfg + i];
-        C[p * cfg + i] -= tau * tmp;
-        for (int r = 1; r < len; r++) C[(p + r) * cfg + i] -= tau * qr[p + r + p * m] * tmp;
-      }
-    }
-  }
-  for (int r = np - 1; r >= 0; r--) {
-    if (i < cfg) {
-      double x = C[r * cfg + i];
-      for (int j = r + 1; j < np; j++) x -= qr[r + j * m] * C[j * cfg + i];
-      C[r * cfg + i] = x / qr[r + r * m];
-    }
-  }
+  hs_colpiv::solve(qr, m, np, hc, C, cfg, lane);
   wave_sync();
   for (int k = 0; k < n; k++) {
     const int col = perm[k];

@@ -666,6 +666,131 @@ size_t hs_sim_estimate_workspace(hs_model_t model, int32_t n_rollouts, int32_t m
  * workspace, and a workspace smaller than hs_sim_estimate_workspace. */
 int hs_sim_estimate_B(hs_model_t model, const hs_sim_estimate_args* args);
 
+/*
+ * Configuration path control (CPC) on the estimated B (additive exports: HSLABS_ABI_VERSION stays 16):
+ * cpccontroller::get_motor_torques (cpc.cpp:215-250) as modelplayer::set_cpc_torques drives it
+ * (player.cpp:465-481), for every rollout of a batch, one wavefront per rollout, HS_PREC_F64 only.
+ * The controller scans every target point (cpccontroller::tpis_subset without efficientdata,
+ * cpc.cpp:437-443); the ball-tree prefilter, poscontrol mode, cost / cost1 and set_ghost_cpc_state are not
+ * restated. All arrays are DEVICE arrays.
+ * Per rollout, in the reference's order: set_current_state + apply_mask (a copy is masked, never the
+ * caller's array); compute_b (cpc.cpp:111-121: b = [-I ; X], Bt_chi X = the left psi = config_dim - nmj
+ * columns of Bt, Bt_chi = its right nmj columns, Eigen 3.3 ColPivHouseholderQR; bbt = b b^T);
+ * compute_prox_loss_over_tps over all n_tp points (cpc.cpp:151-190); candidates (cpc.cpp:252-272): the
+ * n_cand smallest losses, ascending; B_chi_dec = ColPivHouseholderQR(Bt_chi^T); the gain loop
+ * (cpc.cpp:229-237) over cost2 (cpc.cpp:339-362) and controls (cpc.cpp:280-293); last_cand and
+ * tp_dist_check (cpc.cpp:485-494); clip_norm(tau, tauc).
+ * Where the reference is undefined, this library defines the result and says so in flags:
+ *   - map<double, cand> collapses exactly equal losses into one candidate; here ties are kept, the lower
+ *     target point index first (no flag: nothing is lost).
+ *   - a target point whose loss is not finite (denom = 0, e.g. a zero target velocity) sorts after every
+ *     finite loss, lower index first, and HS_CPC_FLAG_NONFINITE is set (the reference keys its map with NaN).
+ *   - if no candidate's score is finite and below cost2's 1e10 (e.g. n_cand = 1 with loss exactly 0: 0 / 0),
+ *     i_best = 0 and HS_CPC_FLAG_NOSCORE is set (the reference indexes column -1).
+ *   - a rank-deficient Bt_chi or B_chi takes Eigen's basic solution, as hs_sim_regress_B does, and
+ *     HS_CPC_FLAG_RANK is set.
+ *   - n_tp < n_cand (the reference iterates past the map's end), n_cand < 1 or > 64, a NULL required
+ *     pointer, a precision other than HS_PREC_F64, a stride too small, or target points beyond the
+ *     kernel's 64 KB of LDS (three doubles and a word per point): HS_E_ARG. So is a k0 that is not finite
+ *     or a kc <= 0, for which the reference's gain loop does not end.
+ */
+#define HS_CPC_FLAG_NONFINITE 1u
+#define HS_CPC_FLAG_NOSCORE 2u
+#define HS_CPC_FLAG_RANK 4u
+
+typedef struct {
+  double w;              /* loss weight of t0 (player.cpp:453: 10) */
+  double sg;             /* goal speed factor (1) */
+  double k0;             /* first gain of the gain loop (200) */
+  double kc;             /* the loop ends once k <= kc (10) */
+  double tauc;           /* torque norm limit (20) */
+  double loss_cc;        /* prox_loss's weight on cc0 + cc1 (cpc.cpp:188: 10) */
+  double tp_dist;        /* tp_dist_check's distance (cpc.cpp:490: 0.5) */
+  int32_t n_cand;        /* candidates (10); 1..64 */
+  int32_t goal_t0s;      /* player.cpp:458: 1 */
+  int32_t tpdist_switch; /* set_flag("goal_t0s") switches it on (cpc.cpp:451): 1 */
+  uint32_t mask;         /* bit i: coordinate i of q and dq is zeroed (cpc.cpp:40-41: {0, 1, 5} = 0x23) */
+} hs_cpc_params;
+
+/* The reference's live values (above). */
+void hs_cpc_default_params(hs_cpc_params* p);
+
+typedef struct {
+  int32_t n_rollouts;
+  int32_t n_tp;            /* target points per set */
+  int32_t precision;       /* HS_PREC_F64 */
+  int32_t reserved;
+  hs_cpc_params params;
+  const double* Bt;        /* [B][nmj][config_dim] (hs_sim_estimate_B) */
+  const double* state;     /* rollout b: q at state + b * state_stride, dq config_dim doubles further (the
+                              tracker's ders[b][0], ders[b][1]) */
+  int64_t state_stride;    /* doubles, >= 2 * config_dim; 3 * config_dim passes hs_sim_track_push's ders as it is */
+  const double* tp;        /* [n_tp][2 * config_dim + nmj] = (q, dq, tau) per target point, masked
+                              (hs_cpc_target_points, or any array of this layout: load_tpset's case) */
+  int64_t tp_stride;       /* doubles between the sets of consecutive rollouts; 0: one set shared by the batch */
+  int32_t* low_tpdist;     /* [B] carried state, read and advanced; starts 1 (cpc.cpp:42) */
+  double* tau;             /* [B][nmj] motor torques */
+  int32_t* last_tpi;       /* [B] last_cand.tpi */
+  uint32_t* flags;         /* [B] HS_CPC_FLAG_* */
+  /* optional diagnostics (NULL to skip) */
+  double* loss;            /* [B][n_tp] */
+  int32_t* cand_tpi;       /* [B][n_cand] ascending loss */
+  double* cand_t0s;        /* [B][n_cand][2] t0 and the s the controls use (sg where goal_t0s applies) */
+  int32_t* passes;         /* [B] passes of the gain loop */
+  int32_t* i_best;         /* [B] */
+  void* stream;            /* hipStream_t */
+} hs_cpc_args;
+
+int hs_cpc_torques(hs_model_t model, const hs_cpc_args* args);
+
+/* cpccontroller::set_target_points_by_per (cpc.cpp:51-63) from the controller tables of hs_sim_args
+ * (q_tab, dq_tab [B][n_t][config_dim], tau_tab [B][n_t][nmj]): tp[b][i] = periodic::get_complete_traj_rec(i)
+ * (periodic.cpp:408-417: sample i, lifted by n_t when i < 2, which is table row (i + n_t - 2) mod n_t),
+ * masked. tp [B][n_t][2 * config_dim + nmj]. HS_PREC_F64 tables only. */
+int hs_cpc_target_points(hs_model_t model, int32_t n_rollouts, int32_t n_t, const double* q_tab, const double* dq_tab,
+                         const double* tau_tab, uint32_t mask, double* tp, void* stream);
+
+/* n_steps of simulate_ode with cpc_control_flag and dynamics_from_simulation_flag (player.cpp:326-340),
+ * enqueued on the stream with no host synchronisation between steps. Per step: hs_sim_estimate_B (pushes
+ * the tracker, probes around tau0); hs_cpc_torques on ders[0..1]; one hs_sim_trial step, open loop, with
+ * the CPC torques as a one-row table (set_ode_motor_torques' clip, the kicks and the fall check come with
+ * it); the torques applied become tau0. A rollout the fall check has frozen keeps body, seed, tsi, its
+ * tau0 row and its per-step output rows. The estimate and the controller still run on it (the launches
+ * cover the batch): its tracker is pushed with the same configuration again (so its rates become 0, every
+ * loss 0 / 0, and its flags HS_CPC_FLAG_NONFINITE | HS_CPC_FLAG_NOSCORE), low_tpdist, last_tpi, flags and
+ * rank are written, and the seed the probes advanced is put back, which costs time and changes nothing
+ * else. A rollout that freezes in step k keeps the seed after step k's estimate, as the reference's process
+ * would have drawn before its fall_check exits. The reference's first two steps (play_t < 2 play_dt -> position control,
+ * player.cpp:468) are the caller's: hs_sim_estimate_B + hs_sim_step for those, so that the tracker has its
+ * two pushes. */
+typedef struct {
+  hs_sim_trial_args trial; /* sim.n_steps = the steps of this call; the tables and open_loop are ignored (the
+                              step is open loop on the CPC torques); sim.precision must be HS_PREC_F64. The
+                              per-step outputs are STEP-major here: tau_cmd / q_meas [n_steps][B][nmj],
+                              torso [n_steps][B][3], n_contacts / normal_force [n_steps][B] */
+  hs_cpc_params cpc;
+  int32_t m;               /* probes per rollout and step (config_dim + 20) */
+  int32_t n_tp;
+  const double* dtau;      /* [n_steps or 1][B][m][nmj] perturbations */
+  int64_t dtau_step_stride;/* doubles between steps; 0 reuses one set */
+  const double* tp;        /* as hs_cpc_args */
+  int64_t tp_stride;
+  double* ders;            /* [B][3][config_dim] tracker, read and advanced */
+  double* tau0;            /* [B][nmj] last motor torques, read and advanced */
+  int32_t* low_tpdist;     /* [B] read and advanced */
+  int32_t* last_tpi;       /* [B] */
+  uint32_t* flags;         /* [B] the last step's HS_CPC_FLAG_* */
+  int32_t* rank;           /* [B] the last step's regression rank */
+  void* workspace;         /* hs_sim_cpc_workspace(model, B, m) bytes, caller-owned, 8-byte aligned */
+  size_t workspace_bytes;
+} hs_sim_cpc_args;
+
+size_t hs_sim_cpc_workspace(hs_model_t model, int32_t n_rollouts, int32_t m);
+
+/* HS_E_ARG for everything hs_sim_estimate_B, hs_cpc_torques and hs_sim_trial reject, and a missing or
+ * small workspace. */
+int hs_sim_cpc_step(hs_model_t model, const hs_sim_cpc_args* args);
+
 /* Host-side handle over the calls above, for callers without device memory of their own
  * (the C++ shim's modelplayer): owns the device tables and state of B rollouts.
  * hs_sim_create = modelplayer::setup_per_controller (player.cpp:370-382) for every rollout:

@@ -1,0 +1,330 @@
+"""GPU checks of configuration path control (hs_cpc_torques, hs_cpc_target_points, hs_sim_cpc_step; DESIGN.md
+section 4b "CPC") against `cpc_reference`, the NumPy restatement of tests/test_cpc_reference.py, on that file's
+fixtures -- whose ordering margins it proves to exceed 1e-6, so every choice must be equal here -- and against
+the Python loop of the parts (estimate_B, cpc_torques, an open-loop trial step).
+
+Bounds: choices (candidate list, passes, i_best, last_tpi, low_tpdist, flags) are equal; loss, t0 / s and the
+torques are held to 1e-10 max(1, |value|): the solves' error is about 1e3 eps cond(B_chi) = 4e-13 at the
+fixtures' cond 1.7, the rest is slack for the sums' order. Measured maxima are printed; on MI355X: loss 3.2e-13,
+t0 / s 4.9e-15, torques 2.9e-14 over the 138 runs of the sweep, 0.0 on the path, and 0.11 of the cond-scaled
+bound on the estimated Bt of the closed-loop test (cond(B_chi) 25 to 346).
+"""
+import os
+
+import numpy as np
+import pytest
+
+from conftest import MODELS, PGS_CONFIG
+from test_cpc_reference import (DIMS, FLAG_NONFINITE, MARGIN, NOISE, check_argument_cases, cpc_reference, make_fixture,
+                                sweep)
+from test_gpu_sim_dynamics import NEVER, copy_state, moved, new_batch
+from test_sim_dynamics import CASES
+
+pytestmark = pytest.mark.gpu
+
+TOL = 1e-10
+EPS = np.finfo(np.float64).eps
+NB = len(NOISE)
+DIAG = dict(loss=True, cand_tpi=True, cand_t0s=True, passes=True, i_best=True)
+
+
+@pytest.fixture(scope="module")
+def gpu(product):
+    import torch
+
+    assert torch.cuda.is_available(), "GPU tests need an MI355X"
+    return product
+
+
+@pytest.fixture(scope="module")
+def models(gpu):
+    return {name: (gpu.KinematicModel(os.path.join(MODELS, f"{name}.xml")), gpu.read_pgs_config(PGS_CONFIG, pid))
+            for name, pid in CASES.items()}
+
+
+@pytest.fixture(scope="module")
+def batches(gpu, models):
+    """name -> a batch of NB rollouts, used only as the controller's handle (its own state is not read)"""
+    res = {name: new_batch(gpu, models, name, n=NB) for name in CASES}
+    for name, sb in res.items():
+        assert (sb.model.config_dim, sb.model.nmj) == DIMS[name]
+    return res
+
+
+@pytest.fixture(scope="module")
+def moved64(gpu, models):
+    return {name: moved(gpu, models, name) for name in CASES}
+
+
+def run_cpc(sb, fx, rollouts, tp=None, low=1, per_rollout_tp=False, **params):
+    """hs_cpc_torques on the fixture's rollouts (padded to the batch with copies of the last one, which are
+    dropped from the result). Returns NumPy arrays, the carried state after the call included."""
+    import torch
+
+    idx = list(rollouts) + [rollouts[-1]] * (sb.B - len(rollouts))
+    Bt = torch.as_tensor(fx["Bt"][idx], device=sb.device)
+    state = torch.as_tensor(np.ascontiguousarray(fx["states"][idx]), device=sb.device)
+    P = sb.cpc_default_params()
+    for k, v in params.items():
+        setattr(P, k, v)
+    tp = fx["tp"] if tp is None else tp
+    if per_rollout_tp:
+        tp = np.ascontiguousarray(np.broadcast_to(tp, (sb.B,) + tp.shape))
+    sb._cpc_state()
+    sb.low_tpdist.fill_(int(low))
+    out = sb.cpc_torques(Bt, tp=tp, params=P, state=state, **DIAG)
+    torch.cuda.synchronize()
+    return {k: v.cpu().numpy()[:len(rollouts)].copy() for k, v in out.items()}
+
+
+def close(got, ref):
+    """max of |got - ref| / max(1, |ref|)"""
+    return float(np.max(np.abs(got - ref) / np.maximum(1.0, np.abs(ref))))
+
+
+def bitwise(a, b, skip=()):
+    for k in a:
+        if k not in skip:
+            assert np.array_equal(a[k], b[k], equal_nan=True), k
+
+
+# ---- 1. the controller against the restatement, on the whole sweep
+def test_controller_matches_reference_on_the_sweep(batches):
+    worst = dict(loss=0.0, cand_t0s=0.0, tau=0.0)
+    n = 0
+    for name, n_tp, nc, tauc, fx, rollouts, refs in sweep():
+        out = run_cpc(batches[name], fx, rollouts, n_cand=nc, tauc=tauc)
+        for i, (j, r) in enumerate(zip(rollouts, refs)):
+            what = (name, n_tp, nc, tauc, j)
+            assert r["margin"] > MARGIN, what
+            assert np.array_equal(out["cand_tpi"][i], r["cand_tpi"]), what
+            assert out["passes"][i] == r["passes"] and out["i_best"][i] == r["i_best"], what
+            assert out["last_tpi"][i] == r["last_tpi"] and out["low_tpdist"][i] == r["low_tpdist"], what
+            assert out["flags"][i] == 0, what
+            for k in worst:
+                d = close(out[k][i], r[k])
+                worst[k] = max(worst[k], d)
+                assert d <= TOL, (what, k, d)
+            n += 1
+    print(f"{n} controller runs; max deviation / max(1, |ref|): " + ", ".join(f"{k} {v:.3e}" for k, v in worst.items()))
+
+
+# ---- 2. the on-path known answer
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_on_path_known_answer(batches, name):
+    cfg, nmj = DIMS[name]
+    worst = 0.0
+    for n_tp, nc in ((70, 10), (10, 10), (130, 4)):
+        fx = make_fixture(name, n_tp)
+        i = int(fx["at"][0])
+        out = run_cpc(batches[name], fx, [0], n_cand=nc, tauc=1e9)
+        assert out["last_tpi"][0] == i and out["cand_tpi"][0, 0] == i and out["i_best"][0] == 0
+        assert out["passes"][0] == 1 and out["flags"][0] == 0 and out["low_tpdist"][0] == 1
+        assert abs(out["cand_t0s"][0, 0, 0]) < 1e-14 and abs(out["cand_t0s"][0, 0, 1] - 1) < 1e-13
+        assert out["loss"][0, i] < 1e-24
+        worst = max(worst, np.abs(out["tau"][0] - fx["tp"][i, 2 * cfg:]).max())
+    print(f"{name}: on the path, max |tau - tau_tp| = {worst:.3e}")
+    assert worst <= 1e-12
+
+
+# ---- 3. shared against per-rollout target points
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_shared_and_per_rollout_target_points_agree(batches, name):
+    fx = make_fixture(name, 70)
+    a = run_cpc(batches[name], fx, range(NB))
+    b = run_cpc(batches[name], fx, range(NB), per_rollout_tp=True)
+    bitwise(a, b)
+    assert len({int(v) for v in a["last_tpi"]}) > 1
+
+
+# ---- 4. a loss that is not finite
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_nonfinite_loss_sorts_last_and_is_flagged(batches, name):
+    cfg, nmj = DIMS[name]
+    for n_tp, nc in ((70, 10), (10, 10)):
+        fx = make_fixture(name, n_tp)
+        z = fx["tp"][n_tp // 2].copy()
+        z[cfg:2 * cfg] = 0  # a target point at rest: denom = 0
+        a = run_cpc(batches[name], fx, range(1, NB), n_cand=nc)
+        b = run_cpc(batches[name], fx, range(1, NB), tp=np.vstack([fx["tp"], z]), n_cand=nc)
+        bitwise(a, b, skip=("flags", "loss"))
+        assert np.array_equal(a["loss"], b["loss"][:, :-1])
+        assert not np.isfinite(b["loss"][:, -1]).any()
+        assert (a["flags"] == 0).all() and (b["flags"] == FLAG_NONFINITE).all()
+
+
+# ---- 5. the carried state
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_low_tpdist_switches_s(batches, name):
+    fx = make_fixture(name, 70)
+    lo = run_cpc(batches[name], fx, range(1, NB), low=0)
+    hi = run_cpc(batches[name], fx, range(1, NB), low=1)
+    assert (hi["cand_t0s"][..., 1] == 1).all()          # sg
+    assert (lo["cand_t0s"][..., 1] != 1).all()          # the candidates' own s
+    assert np.array_equal(lo["cand_t0s"][..., 0], hi["cand_t0s"][..., 0])
+    assert np.array_equal(lo["cand_tpi"], hi["cand_tpi"]) and np.array_equal(lo["loss"], hi["loss"])
+    assert not np.array_equal(lo["tau"], hi["tau"])
+    for j, i in zip(range(1, NB), range(NB - 1)):
+        r = cpc_reference(fx["Bt"][j], fx["states"][j, 0], fx["states"][j, 1], fx["tp"], low_tpdist=0)
+        if r["margin"] > MARGIN:
+            assert lo["last_tpi"][i] == r["last_tpi"] and close(lo["tau"][i], r["tau"]) <= TOL
+        assert close(lo["cand_t0s"][i], r["cand_t0s"]) <= TOL
+    off0 = run_cpc(batches[name], fx, range(1, NB), low=0, tpdist_switch=0)
+    off1 = run_cpc(batches[name], fx, range(1, NB), low=1, tpdist_switch=0)
+    assert (off0["cand_t0s"][..., 1] == 1).all()
+    bitwise(off0, off1)
+    bitwise(off1, hi)
+
+
+# ---- 6. the target points
+def test_target_points_are_the_complete_traj_rows(gpu, models):
+    import torch
+
+    m, p = models["hexapod"]
+    sb = new_batch(gpu, models, "hexapod")
+    tp = sb.cpc_target_points().cpu().numpy()
+    torch.cuda.synchronize()
+    cfg, nmj = m.config_dim, m.nmj
+    ref = gpu.complete_traj(m, [p] * sb.B, sb.n_t)
+    assert tp.shape == ref.shape == (sb.B, sb.n_t, 2 * cfg + nmj)
+    plain = ref.copy()
+    for i in (0, 1, 5):
+        ref[:, :, i] = 0
+        ref[:, :, cfg + i] = 0
+    assert np.array_equal(tp, ref)
+    assert not np.array_equal(tp, plain)  # the mask does act
+    assert np.abs(tp[:, :, 2]).min() > 0  # the torso height is not masked
+    other = sb.cpc_target_points(mask=0b100).cpu().numpy()
+    plain[:, :, 2] = 0
+    plain[:, :, cfg + 2] = 0
+    assert np.array_equal(other, plain)
+
+
+# ---- 7. the closed-loop step
+def python_loop(b, dtau, n_steps):
+    """the parts, step by step: estimate_B -> cpc_torques -> one open-loop trial step with the CPC torques in the
+    table row of each rollout. Returns per step: Bt, ders and low_tpdist as the controller read them, the
+    controller's tau and last_tpi, and tau_cmd."""
+    rec = []
+    keep = b.tables.tau.clone()
+    for k in range(n_steps):
+        est = b.estimate_B(dtau=dtau[k])
+        b._cpc_state()
+        low_in = b.low_tpdist.clone()
+        c = b.cpc_torques(est["Bt"])
+        rows = [b.table_row(int(t)) for t in b.tsi.cpu()]
+        for r, row in enumerate(rows):
+            b.tables.tau[r, row] = c["tau"][r]
+        o = b.trial(1, open_loop=True, check_from=NEVER, tau_cmd=True)
+        b.tables.tau.copy_(keep)
+        rec.append(dict(Bt=est["Bt"].cpu().numpy(), rank=est["rank"].cpu().numpy(), ders=b.ders.cpu().numpy(),
+                        low_in=low_in.cpu().numpy(), tau=c["tau"].cpu().numpy(), last_tpi=c["last_tpi"].cpu().numpy(),
+                        flags=c["flags"].cpu().numpy(), tau_cmd=o["tau_cmd"][:, 0].clone()))
+    return rec
+
+
+def step_dtau(sb, n_steps, seed):
+    import torch
+    from hslabs_amd import synth
+
+    m = sb.model.config_dim + 20
+    d = synth.gen_torque_perturbations(n_steps * sb.B, m, sb.model.nmj, seed=seed)
+    return torch.as_tensor(d.reshape(n_steps, sb.B, m, sb.model.nmj), device=sb.device)
+
+
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_cpc_step_is_the_python_loop(gpu, models, moved64, name):
+    import torch
+
+    src = moved64[name][0]
+    a = copy_state(new_batch(gpu, models, name), src)
+    b = copy_state(new_batch(gpu, models, name), src)
+    n_steps, tauc = 3, a.cpc_default_params().tauc
+    dtau = step_dtau(a, n_steps, seed=21)
+    out = a.cpc_step(n_steps, dtau=dtau, check_from=NEVER, tau_cmd=True)
+    rec = python_loop(b, dtau, n_steps)
+    torch.cuda.synchronize()
+    assert torch.equal(a.body, b.body) and torch.equal(a.seed, b.seed) and torch.equal(a.tsi, b.tsi)
+    assert torch.equal(a.ders, b.ders)
+    assert torch.equal(a.low_tpdist, b.low_tpdist) and torch.equal(a.last_tpi, b.last_tpi)
+    assert (a.tsi == src.tsi + n_steps).all() and (a.state == -1).all()
+    for k in range(n_steps):
+        assert torch.equal(out["tau_cmd"][k], rec[k]["tau_cmd"]), k
+    assert torch.equal(a.last_tau, rec[-1]["tau_cmd"])
+    tc = out["tau_cmd"].cpu().numpy()
+    assert np.isfinite(tc).all()
+    assert (np.linalg.norm(tc, axis=-1) <= tauc * (1 + 1e-12)).all()
+    # against the restatement, on the Bt and the tracker the controller read
+    tp = b._tp.cpu().numpy()
+    cfg, nmj = a.model.config_dim, a.model.nmj
+    ok = total = 0
+    worst = 0.0
+    for k in range(n_steps):
+        for r in range(a.B):
+            e = rec[k]
+            ref = cpc_reference(e["Bt"][r], e["ders"][r, 0], e["ders"][r, 1], tp[r], low_tpdist=int(e["low_in"][r]))
+            cond = np.linalg.cond(e["Bt"][r][:, cfg - nmj:])
+            total += 1
+            print(f"{name} step {k} rollout {r}: cond(B_chi) {cond:.3e}, rank {e['rank'][r]}, flags {e['flags'][r]}, "
+                  f"margin {ref['margin']:.3e} ({min(ref['margins'], key=ref['margins'].get)}), passes {ref['passes']}")
+            if ref["margin"] <= MARGIN:
+                continue
+            ok += 1
+            assert e["last_tpi"][r] == ref["last_tpi"], (k, r)
+            bound = 1e3 * EPS * cond * np.maximum(1.0, np.abs(ref["tau"]))
+            dev = np.abs(e["tau"][r] - ref["tau"])
+            worst = max(worst, float((dev / bound).max()))
+            assert (dev <= bound).all(), (k, r, dev.max(), bound.min())
+    print(f"{name}: {ok} of {total} controller runs have every margin above {MARGIN:g}; worst deviation / bound {worst:.3e}")
+    assert ok > 0
+
+
+def test_cpc_step_reuses_one_perturbation_set(gpu, models, moved64):
+    """a dtau without the step dimension (stride 0) is that set at every step"""
+    import torch
+
+    src = moved64["myant"][0]
+    a = copy_state(new_batch(gpu, models, "myant"), src)
+    b = copy_state(new_batch(gpu, models, "myant"), src)
+    d = step_dtau(a, 1, seed=22)
+    oa = a.cpc_step(2, dtau=d[0], check_from=NEVER, tau_cmd=True)
+    ob = b.cpc_step(2, dtau=torch.cat([d, d]), check_from=NEVER, tau_cmd=True)
+    torch.cuda.synchronize()
+    assert torch.equal(a.body, b.body) and torch.equal(oa["tau_cmd"], ob["tau_cmd"]) and torch.equal(a.seed, b.seed)
+
+
+# ---- 8. a frozen rollout
+def test_frozen_rollout_is_left_alone(gpu, models, moved64):
+    import torch
+
+    src = moved64["hexapod"][0]
+    n_steps, frozen, others = 2, 1, [0, 2]
+    dtau = step_dtau(src, n_steps, seed=23)
+    runs = []
+    for freeze in (True, False):
+        a = copy_state(new_batch(gpu, models, "hexapod"), src)
+        a.state = torch.full((a.B,), -1, dtype=torch.int32, device=a.device)
+        a.fall_z = torch.full((a.B,), float("nan"), dtype=torch.float64, device=a.device)
+        if freeze:
+            a.state[frozen] = 7  # fell at tsi 7, before this call
+        # the fall check is on; hc lies below every torso, so nothing else freezes
+        o = a.cpc_step(n_steps, dtau=dtau, hc=-1.0, check_from=0, tau_cmd=True, torso=True, n_contacts=True, q_meas=True)
+        torch.cuda.synchronize()
+        runs.append((a, o))
+    (a, oa), (b, ob) = runs
+    assert a.state.tolist() == [-1, 7, -1] and (b.state == -1).all()
+    assert torch.equal(a.body[frozen], src.body[frozen]) and a.seed[frozen] == src.seed[frozen]
+    assert a.tsi[frozen] == src.tsi[frozen] and torch.equal(a.last_tau[frozen], src.last_tau[frozen])
+    assert torch.isnan(oa["tau_cmd"][:, frozen]).all() and torch.isnan(oa["torso"][:, frozen]).all()
+    assert torch.isnan(oa["q_meas"][:, frozen]).all() and (oa["n_contacts"][:, frozen] == -1).all()
+    assert not torch.equal(b.body[frozen], src.body[frozen])
+    for k in ("body", "seed", "tsi", "ders", "low_tpdist", "last_tpi", "last_tau"):
+        assert torch.equal(getattr(a, k)[others], getattr(b, k)[others]), k
+    for k in ("tau_cmd", "torso", "n_contacts", "q_meas"):
+        assert torch.equal(oa[k][:, others], ob[k][:, others]), k
+        assert not torch.isnan(ob[k].double()).any()
+
+
+# ---- 9. the argument checks, with a device present
+def test_argument_validation_on_the_device(gpu):
+    check_argument_cases(gpu)
