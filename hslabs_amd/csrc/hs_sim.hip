@@ -377,7 +377,7 @@ __device__ inline void sor_pair(L& s, const RowData<typename L::real>& r, int ro
   delta -= sum;
   delta -= (r.b2 >= 0) ? other : real(0);  // x - 0 == x
   const real lo = (r.rt == ROW_BILATERAL) ? real(-INFINITY) : (r.rt == ROW_NORMAL ? real(0) : -mu);
-  const real hi = (r.rt == ROW_BILATERAL) ? real(INFINITY) : mu;
+  const real hi = (r.rt == ROW_FRICTION) ? mu : real(INFINITY);  // a normal row: [0, inf) whatever mu is
   const real nl = lam + delta;
   const bool below = nl < lo, above = !below && nl > hi;
   const real newl = below ? lo : (above ? hi : nl);

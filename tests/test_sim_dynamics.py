@@ -56,11 +56,12 @@ def lcg_jump(seed, k):
     return seed
 
 
-def oracle_probes(O, om, body, seed, taus):
+def oracle_probes(O, om, body, seed, taus, params=None):
     """The reference's probe loop for one rollout: from `body` (restored every time) one step with
     each row of taus [m][nmj] applied as it is, the seed carried from probe to probe. Returns the
-    stepped bodies [m][n][13], n_contacts [m] and the m + 1 seeds."""
-    P = O.SimParams(k=1e-300)
+    stepped bodies [m][n][13], n_contacts [m] and the m + 1 seeds. params: the step's SimParams
+    (with k = 1e-300, so that the table row is the torque), default SimParams(k=1e-300)."""
+    P = O.SimParams(k=1e-300) if params is None else params
     cfg = 6 + taus.shape[1]
     z = np.zeros((2, cfg))
     bodies, ncs, seeds = [], [], [int(seed)]

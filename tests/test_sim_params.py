@@ -1,0 +1,364 @@
+"""Every field of hs_sim_params against the oracle, off the GPU: the table of parameter sets and the
+scenarios the GPU tests (tests/test_gpu_sim_params.py) run, and the oracle-only conditions those
+tests rest on.
+
+hs_sim_params has eleven fields (dt, k, sor_w, erp, cfm, gravity, bounce, bounce_vel, soft_cfm, mu,
+iterations); branches of the simulation kernel hang on several (the friction clamp at +-mu, the
+bounce branch, the partial last block of sweeps, the reshuffle count, k > 0, gravity != 0).
+PARAM_SETS changes each of them from its default; `scenario` makes the states they are run from:
+  stand  the reset state at table row 0;
+  land   the same state with every body lifted by 0.05 and given lvel z = -1: it touches down at
+         about step 5, far above bounce_vel;
+  sunk   every body centre at z = 0 (tests/test_gpu_sim.py::test_every_part_in_contact): the
+         maximum row count.
+Checked here, on oracle/hs_oracle_sim.cpp alone (hexapod and myant, STEPS = 12):
+  * every set is felt: its final body state differs from the default's by more than FELT = 1e-6,
+    1e4 times the comparison bound BODY_TOL (on land; k = 0 on stand);
+  * the contact counts on land span {0, ..., 4} on the hexapod, so several row counts occur;
+  * sensitivity: a rounding-sized (2e-16 relative) perturbation of the torque table -- the size of
+    the kernel's fused SOR sums -- moves no contact count and the final body state by less than
+    BODY_TOL / 100. A perturbation of the start positions would flip stance contacts (a planned
+    stance foot sits on the depth >= 0 threshold), so both sides of every comparison start from
+    bitwise the same state;
+  * which sets discriminate in single precision: the oracle's own distance between the set's and the
+    defaults' final torso state (body 0's position, quaternion and velocities; 8 rollouts on land)
+    exceeds F32_D_OTHER (at least 12 sets);
+  * the argument checks of hs_sim_step and hs_sim_trial on mu, dt and iterations, decided before any
+    device call.
+"""
+import ctypes
+import os
+
+import numpy as np
+import pytest
+
+from conftest import MODELS, record_to_oracle_gait
+
+STEPS = 12
+TSI0 = 2
+BODY_TOL = 1e-10       # tests/test_gpu_sim.py
+FELT = 1e-6            # 1e4 * BODY_TOL
+SENS_TOL = 1e-12       # BODY_TOL / 100
+F32_D_OTHER = 1e-2     # a set discriminates in fp32 when it moves the torso by more than this
+F32_MIN_SETS = 12
+F32_ROLLOUTS = 8
+# the fewest rollouts that keep the conditions below true (three hexapods never show two contacts)
+CPU_ROLLOUTS = {"hexapod": 4, "myant": 2}
+
+# each set is a change of the defaults (SimParams() / hs_sim_default_params)
+PARAM_SETS = {
+    # finite friction: the clamp at +-mu in sor_pair
+    "mu=0.5": dict(mu=0.5),
+    "mu=0.05": dict(mu=0.05),
+    # sweep count: no sweep and no draw; a lone partial block; exact blocks; 8 + 1; five reshuffles
+    "iterations=0": dict(iterations=0),
+    "iterations=1": dict(iterations=1),
+    "iterations=7": dict(iterations=7),
+    "iterations=8": dict(iterations=8),
+    "iterations=9": dict(iterations=9),
+    "iterations=33": dict(iterations=33),
+    # solver constants: the row build, Ad
+    "sor_w=1.0": dict(sor_w=1.0),
+    "erp=0.2": dict(erp=0.2),
+    "cfm=1e-5": dict(cfm=1e-5),
+    "soft_cfm=0": dict(soft_cfm=0.0),
+    # bounce: the branch off; always on
+    "bounce_vel=-1": dict(bounce_vel=-1.0),
+    "bounce=0.9,bounce_vel=0": dict(bounce=0.9, bounce_vel=0.0),
+    # gravity: the != 0 switch; large normal forces
+    "gravity=0": dict(gravity=0.0),
+    "gravity=9.81": dict(gravity=9.81),
+    # step size: n_t = 600 tables
+    "dt=0.005": dict(dt=0.005),
+    # PD gain: k1 and k2; torques off with contacts (stand only)
+    "k=25": dict(k=25.0),
+    "k=0": dict(k=0.0),
+    # several at once
+    "mixed": dict(mu=0.5, iterations=9, sor_w=1.0, bounce_vel=0.0),
+}
+STAND_ONLY = ("k=0",)
+SUNK_SETS = ("mu=0.5", "mu=0.05", "mixed")
+
+
+def set_dt(name):
+    return PARAM_SETS[name].get("dt", 0.01)
+
+
+def set_n_t(name, period=3.0):
+    """SimBatch's table length for the set's dt: int(T / dt + .5)"""
+    return int(period / set_dt(name) + .5)
+
+
+def scenario(body0, which):
+    """The start state `which` from reset states body0 [...][n][13] (pos, quaternion, lvel, avel); a copy
+    of body0's own type (NumPy array or torch tensor) and precision."""
+    b = body0.copy() if isinstance(body0, np.ndarray) else body0.clone()
+    if which == "stand":
+        return b
+    if which == "land":
+        b[..., 2] += 0.05
+        b[..., 9] = -1.0
+        return b
+    if which == "sunk":
+        b[..., 2] = 0.0
+        return b
+    raise ValueError(f"unknown scenario {which!r}")
+
+
+def scenario_of(name):
+    return "stand" if name in STAND_ONLY else "land"
+
+
+def perturbed(tt, seed=0):
+    """the torque table moved by 2e-16 relative, every entry up or down"""
+    sign = np.random.default_rng(seed).integers(0, 2, tt.shape) * 2.0 - 1.0
+    return tt * (1.0 + 2e-16 * sign)
+
+
+def oracle_tables(O, om, name, n_rollouts, n_t):
+    """[(q_tab, dq_tab, tau_tab)] of the first rollouts of synth.gen_sim_params(., name)"""
+    from hslabs_amd import synth
+
+    recs = synth.gen_sim_params(n_rollouts, name)
+    return [O.controller_tables(om, record_to_oracle_gait(O, r), n_t) for r in recs]
+
+
+def run_set(O, om, tabs, pname, which, steps=STEPS, tau_tab=None):
+    """one rollout of `steps` steps under PARAM_SETS[pname] from scenario `which` of the reset state"""
+    qt, dqt, tt = tabs
+    body = scenario(O.sim_reset(om, qt[0]), which)
+    P = O.SimParams(**PARAM_SETS[pname]) if pname else O.SimParams()
+    return O.sim_run(om, P, qt.shape[0], qt, dqt, tt if tau_tab is None else tau_tab, body, 0, TSI0, steps)
+
+
+@pytest.fixture(scope="module")
+def runs(oracle_mod, omodels):
+    """(model, set or None for the defaults, scenario, rollout) -> the oracle's run; computed once, read only.
+    tabs: (model, n_t) -> the rollouts' tables."""
+    O = oracle_mod
+    tabs, res = {}, {}
+    for model, nb in CPU_ROLLOUTS.items():
+        for n_t in (300, 600):
+            tabs[model, n_t] = oracle_tables(O, omodels[model], model, nb, n_t)
+        for pname in [None] + list(PARAM_SETS):
+            n_t = set_n_t(pname) if pname else 300
+            for which in ("stand", "land"):
+                for b in range(nb):
+                    res[model, pname, which, b] = run_set(O, omodels[model], tabs[model, n_t][b], pname, which)
+    return tabs, res
+
+
+def test_table_covers_every_field(oracle_mod):
+    fields = set(vars(oracle_mod.SimParams()))
+    assert len(fields) == 11
+    changed = set().union(*[set(v) for v in PARAM_SETS.values()])
+    assert changed == fields, fields - changed
+    assert sorted(PARAM_SETS[n]["iterations"] for n in PARAM_SETS if n.startswith("iterations")) == [0, 1, 7, 8, 9, 33]
+    assert set(SUNK_SETS) <= set(PARAM_SETS) and set(STAND_ONLY) <= set(PARAM_SETS)
+    assert set_n_t("dt=0.005") == 600 and set_n_t("mixed") == 300
+
+
+def test_scenarios():
+    b = np.arange(2 * 3 * 13, dtype=np.float64).reshape(2, 3, 13)
+    keep = b.copy()
+    assert np.array_equal(scenario(b, "stand"), b) and scenario(b, "stand") is not b
+    ld = scenario(b, "land")
+    assert np.array_equal(ld[..., 2], b[..., 2] + 0.05) and (ld[..., 9] == -1).all()
+    mask = np.ones(13, bool)
+    mask[[2, 9]] = False
+    assert np.array_equal(ld[..., mask], b[..., mask])
+    sk = scenario(b, "sunk")
+    mask[9] = True
+    assert (sk[..., 2] == 0).all() and np.array_equal(sk[..., mask], b[..., mask])
+    assert np.array_equal(b, keep)
+    assert scenario(b.astype(np.float32), "land").dtype == np.float32
+    with pytest.raises(ValueError):
+        scenario(b, "fly")
+
+
+def test_each_set_is_felt(runs):
+    """a condition, not a measurement: a set that fails it gets another value, the threshold stays"""
+    _, res = runs
+    for pname in PARAM_SETS:
+        which = scenario_of(pname)
+        d = max(np.abs(res[model, pname, which, b]["body"] - res[model, None, which, b]["body"]).max()
+                for model, nb in CPU_ROLLOUTS.items() for b in range(nb))
+        print(f"{pname:26s} {which:5s}: final body state differs from the defaults' by {d:.3e}")
+        assert d > FELT, pname
+
+
+def test_the_reshuffle_count_is_the_seeds(runs):
+    """the dRand seed after a run pins the draws: rows - 1 per reshuffle, (iterations + 7) / 8 reshuffles
+    per step -- so an equal seed on the GPU is an equal number of draws"""
+    from test_sim_dynamics import lcg_jump
+
+    _, res = runs
+    for pname in [n for n in PARAM_SETS if n.startswith("iterations")] + ["mixed", None]:
+        its = PARAM_SETS[pname]["iterations"] if pname else 20
+        r = res["hexapod", pname, "land", 0]
+        rows = 108 + 3 * r["n_contacts"]  # hexapod: 108 joint rows (test_every_part_in_contact)
+        draws = int(((rows - 1) * ((its + 7) // 8)).sum())
+        assert lcg_jump(0, draws) == r["seed"], pname
+        assert (r["seed"] == 0) == (its == 0)
+
+
+def test_contact_count_variety(runs):
+    _, res = runs
+    seen = set()
+    for b in range(CPU_ROLLOUTS["hexapod"]):
+        seen |= set(res["hexapod", None, "land", b]["n_contacts"].tolist())
+    print("hexapod, land, defaults: contact counts", sorted(seen))
+    assert set(range(5)) <= seen, seen
+
+
+def test_sensitivity(oracle_mod, omodels, runs):
+    """the bounds of the GPU comparison (BODY_TOL) against a rounding-sized perturbation"""
+    tabs, res = runs
+    worst = 0.0
+    for pname in PARAM_SETS:
+        d = 0.0
+        for model, nb in CPU_ROLLOUTS.items():
+            for which in ("stand", "land"):
+                for b in range(nb):
+                    t = tabs[model, set_n_t(pname)][b]
+                    p = run_set(oracle_mod, omodels[model], t, pname, which, tau_tab=perturbed(t[2], seed=b))
+                    r = res[model, pname, which, b]
+                    assert np.array_equal(p["n_contacts"], r["n_contacts"]), (pname, model, which, b)
+                    d = max(d, np.abs(p["body"] - r["body"]).max())
+        print(f"{pname:26s}: 2e-16 relative on the torque table moves the final body state by {d:.3e}")
+        assert d < SENS_TOL, pname
+        worst = max(worst, d)
+    print(f"sensitivity: maximum over the sets {worst:.3e} (bound {SENS_TOL:.0e} = BODY_TOL / 100)")
+
+
+def torso_distance(body_a, body_b):
+    """the largest difference of the torso body's state (body 0: position, quaternion, lvel, avel) over the
+    rollouts of two final states [...][n][13]"""
+    return float(np.abs(np.asarray(body_a, dtype=np.float64)[..., 0, :] -
+                        np.asarray(body_b, dtype=np.float64)[..., 0, :]).max())
+
+
+def f32_d_other(O, om, tabs, pname, tabs_default=None):
+    """d_other of the fp32 check: the oracle's own torso distance, after STEPS steps on land, between
+    PARAM_SETS[pname] and the defaults, over the rollouts of tabs. Returns (d_other, the set's final
+    bodies [B][n][13])."""
+    mine = np.array([run_set(O, om, t, pname, "land")["body"] for t in tabs])
+    base = np.array([run_set(O, om, t, None, "land")["body"] for t in (tabs_default or tabs)])
+    return torso_distance(mine, base), mine
+
+
+def test_sets_that_discriminate_in_fp32(oracle_mod, omodels):
+    """single precision cannot follow the oracle step for step; what a GPU test can ask is that the fp32
+    kernel sits nearer its own set's answer than the defaults'. That needs the set to move the torso by
+    much more than float trajectories drift: d_other > F32_D_OTHER (B = 8, land, STEPS steps)."""
+    for model in CPU_ROLLOUTS:
+        tabs = {n_t: oracle_tables(oracle_mod, omodels[model], model, F32_ROLLOUTS, n_t) for n_t in (300, 600)}
+        d = {p: f32_d_other(oracle_mod, omodels[model], tabs[set_n_t(p)], p, tabs[300])[0] for p in PARAM_SETS}
+        ok = [p for p in PARAM_SETS if d[p] > F32_D_OTHER]
+        for p in PARAM_SETS:
+            print(f"{model} {p:26s}: torso distance from the defaults on land {d[p]:.3e}"
+                  f"{'' if p in ok else '  (does not qualify)'}")
+        print(f"{model}: {len(ok)} sets qualify; not: {[p for p in PARAM_SETS if p not in ok]}")
+        assert len(ok) >= F32_MIN_SETS, (model, ok)
+        assert "cfm=1e-5" not in ok
+
+
+# ---- kicks under a parameter set: the emulation of tests/test_sim_trial.py (oracle_trial), which knows the
+# default parameters alone, with the set's: dv added to the root body's lvel before the kicked step
+KICK_EVERY, KICK_PHASE = 1000, 5   # one kick, before the step at tsi = 5
+KICK_DV = ((0.0, 0.0, 0.0), (0.0, 10.0, 0.0), (3.0, -4.0, 2.0), (0.0, 0.0, -5.0))
+
+
+def oracle_kicked(O, om, P, n_t, qt, dqt, tt, body0, n_steps, dv):
+    """n_steps under P from body0 (tsi TSI0, seed 0), one step at a time, kicked as oracle_trial kicks;
+    the per-step outputs stacked, with the final body and seed"""
+    body, seed, tsi = np.array(body0, dtype=np.float64), 0, TSI0
+    out = dict(tau_cmd=[], q_meas=[], torso=[], n_contacts=[])
+    for _ in range(n_steps):
+        b = body.copy()
+        if tsi % KICK_EVERY == KICK_PHASE:
+            b[0, 7:10] += dv
+        r = O.sim_run(om, P, n_t, qt, dqt, tt, b, seed, tsi, 1)
+        body, seed, tsi = r["body"], r["seed"], r["tsi"]
+        for k in out:
+            out[k].append(r[k][0])
+    res = {k: np.array(v) for k, v in out.items()}
+    res.update(body=body, seed=seed)
+    return res
+
+
+def test_kick_emulation_without_a_kick_is_the_oracles_run(oracle_mod, omodels, runs):
+    tabs, res = runs
+    qt, dqt, tt = tabs["hexapod", 300][0]
+    P = oracle_mod.SimParams(**PARAM_SETS["gravity=0"])
+    body0 = scenario(oracle_mod.sim_reset(omodels["hexapod"], qt[0]), "land")
+    a = oracle_kicked(oracle_mod, omodels["hexapod"], P, 300, qt, dqt, tt, body0, STEPS, np.zeros(3))
+    r = res["hexapod", "gravity=0", "land", 0]
+    assert np.array_equal(a["body"], r["body"]) and a["seed"] == r["seed"]
+    assert np.array_equal(a["tau_cmd"], r["tau_cmd"]) and np.array_equal(a["torso"], r["torso"])
+    k = oracle_kicked(oracle_mod, omodels["hexapod"], P, 300, qt, dqt, tt, body0, STEPS, np.array(KICK_DV[1]))
+    at = KICK_PHASE - TSI0  # the kicked step
+    assert np.array_equal(k["torso"][:at], r["torso"][:at])
+    assert abs(k["torso"][at, 1] - r["torso"][at, 1]) > 1e-3  # the kick acts (10 * dt, less what the legs take)
+
+
+# ---- argument checks, no device
+def check_sim_param_arguments(product):
+    """HS_E_ARG of hs_sim_step and hs_sim_trial on the parameter fields; every case is decided before any
+    device call, so the pointers only need to be non-NULL"""
+    capi = product.capi
+    L = capi.load()
+    m = product.KinematicModel(os.path.join(MODELS, "hexapod.xml"))
+    x = ctypes.create_string_buffer(64)
+    p = ctypes.addressof(x)
+    E = -1  # HS_E_ARG
+    nan = float("nan")
+
+    def fill(a, **kw):
+        a.n_rollouts, a.n_steps, a.n_t, a.precision = 1, 1, 300, capi.HS_PREC_F64
+        a.params = product.SimBatch.default_params()
+        for f in ("body", "seed", "tsi", "q_tab", "dq_tab", "tau_tab"):
+            setattr(a, f, p)
+        for k, v in kw.items():
+            setattr(a.params, k, v)
+
+    def step(**kw):
+        a = capi.SimArgsC()
+        fill(a, **kw)
+        return L.hs_sim_step(m.handle, ctypes.byref(a))
+
+    def trial(**kw):
+        t = capi.SimTrialArgsC()
+        fill(t.sim, **kw)
+        t.state = p
+        return L.hs_sim_trial(m.handle, ctypes.byref(t))
+
+    for call in (step, trial):
+        for mu in (0.0, -1.0, nan):
+            assert call(mu=mu) == E, (call.__name__, mu)
+            assert b"mu" in L.hs_last_error()
+        for dt in (0.0, nan):
+            assert call(dt=dt) == E, (call.__name__, dt)
+            assert b"dt" in L.hs_last_error()
+        assert call(iterations=-1) == E, call.__name__
+        assert b"iterations" in L.hs_last_error()
+
+    # iterations = 0 is not rejected at that stage. No call here may reach the device (the pointers are
+    # not device memory), so a later check ends it: without a table the complaint is the table, where
+    # iterations = -1 in the same call is the complaint itself. The GPU tests run iterations = 0.
+    for its, word in ((0, b"tables"), (-1, b"iterations")):
+        a = capi.SimArgsC()
+        fill(a, iterations=its)
+        a.q_tab = None
+        assert L.hs_sim_step(m.handle, ctypes.byref(a)) == E
+        assert word in L.hs_last_error(), (its, L.hs_last_error())
+        t = capi.SimTrialArgsC()
+        fill(t.sim, iterations=its)
+        t.state = p
+        t.sim.q_tab = None
+        assert L.hs_sim_trial(m.handle, ctypes.byref(t)) == E
+        assert word in L.hs_last_error(), (its, L.hs_last_error())
+
+
+def test_argument_validation(product):
+    check_sim_param_arguments(product)
