@@ -11,8 +11,9 @@ work_dt *= dt; work += work_dt (periodic.cpp:301-302, `work_add` under
 `#pragma clang fp contract(off)`): plain -ffp-contract=fast ignores that pragma
 and emitted one v_fmac_f64 there; tools/isa_check.py's
 `work_add_check` verifies the reduce kernel's ISA.
-The closed-loop simulation (hs_sim.hip, and hs_sim_trial.hip and hs_sim_probe.hip which include it, and the
-configuration path controller hs_cpc.hip that runs on its estimates) is the exception, built with
+The closed-loop simulation (hs_sim.hip, hs_sim_trial.hip and hs_sim_probe.hip, the three units of the
+kernel in hs_sim_kernel.h, and the configuration path controller hs_cpc.hip that runs on its estimates) is
+the exception, built with
 -ffp-contract=off: its contact test (depth >= 0) is decided within rounding for
 stance feet, so it keeps the oracle's unfused rounding (a per-file flag).
 So is hs_config.hip (the per-configuration FK / IK of the model.h API), which is
@@ -37,7 +38,7 @@ SOURCES = ["hs_kernels.hip", "hs_kernels_f32.hip", "hs_sim.hip", "hs_sim_trial.h
 # (same SONAME) is the one bound
 LIBS = ["-L/opt/rocm/lib", "-lrccl"]
 VARIANT_DIR = os.path.join(OUT_DIR, "variants")
-HEADERS = ["hs_topo.h", "hs_simtopo.h", "hs_ode.h", "hs_math.h", "hs_internal.h", "hs_sim_config.h", "hs_limb.h", "hs_limb_tile.h", "hs_colpiv.h", os.path.join("..", "..", "include", "hslabs.h")]
+HEADERS = ["hs_topo.h", "hs_simtopo.h", "hs_ode.h", "hs_math.h", "hs_internal.h", "hs_sim_kernel.h", "hs_sim_config.h", "hs_limb.h", "hs_limb_tile.h", "hs_colpiv.h", os.path.join("..", "..", "include", "hslabs.h")]
 ARCH = os.environ.get("HSLABS_ARCH", "gfx950")
 # per-source FMA contraction (default: fast, except where a `#pragma clang fp contract(off)` says not)
 CONTRACT = {"hs_sim.hip": "off", "hs_sim_trial.hip": "off", "hs_sim_probe.hip": "off", "hs_cpc.hip": "off", "hs_config.hip": "off"}

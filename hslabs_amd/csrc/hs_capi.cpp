@@ -126,36 +126,39 @@ int device_state(hs_model_t m, int n_rollouts, void* stream, const hs_topo** top
   return HS_OK;
 }
 
-// Device copies of the topology and the ODE world description for the current device.
-int sim_device_state(hs_model_t m, const hs_topo** topo, const hs_simtopo** sim,
-                     const hs_simtopo_t<float>** sim_f32 = nullptr) {
-  int rc = device_state(m, 0, nullptr, topo, nullptr);
-  if (rc != HS_OK) return rc;
+// What the simulation launchers take (hs::sim_dev): the device copies of the topology and of the ODE world
+// for the current device, created once per device, the rounded world with HS_PREC_F32 only. *rc: HS_OK, or
+// the failure (recorded for hs_last_error()).
+hs::sim_dev sim_dev_of(hs_model_t m, int32_t precision, int* rc) {
+  hs::sim_dev dv{nullptr, nullptr, nullptr, m->sim};
+  auto failed = [&](hipError_t e, const char* what) { *rc = hip_fail(e, what); return dv; };
+  *rc = device_state(m, 0, nullptr, &dv.topo, nullptr);
+  if (*rc != HS_OK) return dv;
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return hip_fail(e, "hipGetDevice");
+  if (e != hipSuccess) return failed(e, "hipGetDevice");
   std::lock_guard<std::mutex> lk(m->mu);
   if (!m->sim_dev[dev]) {
     hs_simtopo* d = nullptr;
     e = hipMalloc(&d, sizeof(hs_simtopo));
-    if (e != hipSuccess) return hip_fail(e, "hipMalloc(simtopo)");
+    if (e != hipSuccess) return failed(e, "hipMalloc(simtopo)");
     e = hipMemcpy(d, &m->sim, sizeof(hs_simtopo), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(d); return hip_fail(e, "hipMemcpy(simtopo)"); }
+    if (e != hipSuccess) { (void)hipFree(d); return failed(e, "hipMemcpy(simtopo)"); }
     m->sim_dev[dev] = d;
   }
-  if (sim_f32 && !m->sim_dev_f32[dev]) {
+  if (precision == HS_PREC_F32 && !m->sim_dev_f32[dev]) {
     hs_simtopo_t<float> h;
     hs_simtopo_round(h, m->sim);
     hs_simtopo_t<float>* d = nullptr;
     e = hipMalloc(&d, sizeof(h));
-    if (e != hipSuccess) return hip_fail(e, "hipMalloc(simtopo f32)");
+    if (e != hipSuccess) return failed(e, "hipMalloc(simtopo f32)");
     e = hipMemcpy(d, &h, sizeof(h), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(d); return hip_fail(e, "hipMemcpy(simtopo f32)"); }
+    if (e != hipSuccess) { (void)hipFree(d); return failed(e, "hipMemcpy(simtopo f32)"); }
     m->sim_dev_f32[dev] = d;
   }
-  *sim = m->sim_dev[dev];
-  if (sim_f32) *sim_f32 = m->sim_dev_f32[dev];
-  return HS_OK;
+  dv.sim = m->sim_dev[dev];
+  if (precision == HS_PREC_F32) dv.sim_f32 = m->sim_dev_f32[dev];
+  return dv;
 }
 
 // switch_torso_penalty other than (1,1): the closed form solves the (1,1) problem, so every step of
@@ -1340,7 +1343,7 @@ void hs_best_key_decode(uint64_t key, float* cot, int64_t* id) {
 }  // extern "C"
 
 // ---------------------------------------------------------------------------
-// closed-loop simulation (hs_sim.hip)
+// closed-loop simulation (hs_sim.hip, hs_sim_trial.hip, hs_sim_probe.hip)
 // ---------------------------------------------------------------------------
 extern "C" {
 
@@ -1360,21 +1363,57 @@ void hs_sim_default_params(hs_sim_params* p) {
   p->iterations = 20;    // ODE dWorldSetQuickStepNumIterations default
 }
 
+// ---- the argument rules the simulation's entry points share, each with its message
+// a count of rollouts (msg: the caller's message, which names the count as its arguments do)
+static int count_check(int32_t n, const char* msg) { return (n < 0 || n > (1 << 30)) ? fail(HS_E_ARG, msg) : HS_OK; }
+
+// either precision, or double alone for the parts that exist in double only (f64_only: their message)
+static int precision_check(int32_t precision, const char* f64_only = nullptr) {
+  if (f64_only) return precision == HS_PREC_F64 ? HS_OK : fail(HS_E_ARG, f64_only);
+  return (precision == HS_PREC_F64 || precision == HS_PREC_F32) ? HS_OK : fail(HS_E_ARG, "unknown precision");
+}
+
+// the fields of hs_sim_params the kernel cannot take as they come, and the model's size
+static int sim_params_check(hs_model_t m, const hs_sim_params& P) {
+  if (!(P.dt > 0)) return fail(HS_E_ARG, "dt must be > 0");
+  if (P.iterations < 0) return fail(HS_E_ARG, "iterations < 0");
+  if (!(P.mu > 0)) return fail(HS_E_ARG, "mu must be > 0 (the reference uses dInfinity: 3 rows per contact)");
+  if (m->sim.m_max > 9 * HS_NMAX) return fail(HS_E_TOPOLOGY, "too many constraint rows for the simulation kernel");
+  return HS_OK;
+}
+
+// the settings hs_sim_trial adds to hs_sim_step's
+static int trial_extras_check(const hs_sim_trial_args& t) {
+  if (!(t.torque_limit >= 0)) return fail(HS_E_ARG, "torque_limit must be >= 0 (0: no limit)");
+  if (t.kick_every > 0) {
+    if (t.kick_phase < 0 || t.kick_phase >= t.kick_every)
+      return fail(HS_E_ARG, "kick_phase must lie in [0, kick_every)");
+    if (!t.kick_dv) return fail(HS_E_ARG, "kick_dv is required when kick_every > 0");
+  }
+  return HS_OK;
+}
+
+// the row stride of a set of target points (0: one set shared by the rollouts)
+static int tp_stride_check(hs_model_t m, int64_t tp_stride, int32_t n_tp) {
+  if (tp_stride != 0 && tp_stride < (int64_t)n_tp * (2 * m->host.cfg + m->sim.nmj))
+    return fail(HS_E_ARG, "tp_stride smaller than one set of target points (0: a shared set)");
+  return HS_OK;
+}
+
 int hs_sim_reset(hs_model_t m, int32_t n_rollouts, const double* config, int32_t config_stride, double* body,
                  int32_t precision, void* stream) {
   if (!m) return fail(HS_E_ARG, "null model");
-  if (n_rollouts < 0 || n_rollouts > (1 << 30)) return fail(HS_E_ARG, "bad n_rollouts");
+  int rc = count_check(n_rollouts, "bad n_rollouts");
+  if (rc != HS_OK) return rc;
   if (n_rollouts == 0) return HS_OK;
   if (!config || !body) return fail(HS_E_ARG, "null config or body");
   if (config_stride < m->host.cfg) return fail(HS_E_ARG, "config_stride < config_dim");
-  if (precision != HS_PREC_F64 && precision != HS_PREC_F32) return fail(HS_E_ARG, "unknown precision");
-  const hs_topo* d = nullptr;
-  const hs_simtopo* ds = nullptr;
-  int rc = sim_device_state(m, &d, &ds);
+  if ((rc = precision_check(precision)) != HS_OK) return rc;
+  // the pose is built from the double world whatever the state's precision
+  const hs::sim_dev dv = sim_dev_of(m, HS_PREC_F64, &rc);
   if (rc != HS_OK) return rc;
-  int e = hs::launch_sim_reset(d, ds, n_rollouts, config, config_stride, body, precision, stream);
-  if (e != 0) return hip_fail((hipError_t)e, "hs_sim_reset launch");
-  return HS_OK;
+  int e = hs::launch_sim_reset(dv, n_rollouts, config, config_stride, body, precision, stream);
+  return e ? hip_fail((hipError_t)e, "hs_sim_reset launch") : HS_OK;
 }
 
 // the checks hs_sim_step and hs_sim_trial share; *nothing = 1 for an empty call. open_loop reads
@@ -1382,18 +1421,15 @@ int hs_sim_reset(hs_model_t m, int32_t n_rollouts, const double* config, int32_t
 static int sim_args_check(hs_model_t m, const hs_sim_args* a, bool open_loop, bool* nothing) {
   *nothing = false;
   if (!m || !a) return fail(HS_E_ARG, "null model or args");
-  if (a->n_rollouts < 0 || a->n_rollouts > (1 << 30)) return fail(HS_E_ARG, "bad n_rollouts");
+  if (int rc = count_check(a->n_rollouts, "bad n_rollouts"); rc != HS_OK) return rc;
   if (a->n_steps < 0) return fail(HS_E_ARG, "n_steps < 0");
   if (a->n_rollouts == 0 || a->n_steps == 0) {
     *nothing = true;
     return HS_OK;
   }
   if (!a->body || !a->seed || !a->tsi) return fail(HS_E_ARG, "body, seed and tsi are required");
-  const hs_sim_params& P = a->params;
-  if (!(P.dt > 0)) return fail(HS_E_ARG, "dt must be > 0");
-  if (P.iterations < 0) return fail(HS_E_ARG, "iterations < 0");
-  if (!(P.mu > 0)) return fail(HS_E_ARG, "mu must be > 0 (the reference uses dInfinity: 3 rows per contact)");
-  if (P.k > 0) {
+  if (int rc = sim_params_check(m, a->params); rc != HS_OK) return rc;
+  if (a->params.k > 0) {
     if (a->n_t < 1) return fail(HS_E_ARG, "n_t must be >= 1 with position control");
     if (!a->q_tab || !a->dq_tab || !a->tau_tab) return fail(HS_E_ARG, "controller tables are required when k > 0");
   }
@@ -1401,25 +1437,19 @@ static int sim_args_check(hs_model_t m, const hs_sim_args* a, bool open_loop, bo
     if (a->n_t < 1) return fail(HS_E_ARG, "n_t must be >= 1 with open-loop torques");
     if (!a->tau_tab) return fail(HS_E_ARG, "the torque table is required with open_loop");
   }
-  if (m->sim.m_max > 9 * HS_NMAX) return fail(HS_E_TOPOLOGY, "too many constraint rows for the simulation kernel");
-  if (a->precision != HS_PREC_F64 && a->precision != HS_PREC_F32) return fail(HS_E_ARG, "unknown precision");
-  return HS_OK;
+  return precision_check(a->precision);
 }
 
 int hs_sim_step(hs_model_t m, const hs_sim_args* a) {
   bool nothing = false;
   int rc = sim_args_check(m, a, false, &nothing);
   if (rc != HS_OK || nothing) return rc;
-  const hs_topo* d = nullptr;
-  const hs_simtopo* ds = nullptr;
-  const hs_simtopo_t<float>* dsf = nullptr;
-  rc = sim_device_state(m, &d, &ds, a->precision == HS_PREC_F32 ? &dsf : nullptr);
+  const hs::sim_dev dv = sim_dev_of(m, a->precision, &rc);
   if (rc != HS_OK) return rc;
   hs_sim_args c = *a;
   if (c.n_t < 1) c.n_t = 1;
-  int e = hs::launch_sim_steps(d, ds, dsf, m->sim, c);
-  if (e != 0) return hip_fail((hipError_t)e, "hs_sim_step launch");
-  return HS_OK;
+  int e = hs::launch_sim_steps(dv, c);
+  return e ? hip_fail((hipError_t)e, "hs_sim_step launch") : HS_OK;
 }
 
 int hs_sim_trial(hs_model_t m, const hs_sim_trial_args* t) {
@@ -1428,25 +1458,16 @@ int hs_sim_trial(hs_model_t m, const hs_sim_trial_args* t) {
   bool nothing = false;
   int rc = sim_args_check(m, a, t->open_loop != 0, &nothing);
   if (rc != HS_OK) return rc;
-  if (!(t->torque_limit >= 0)) return fail(HS_E_ARG, "torque_limit must be >= 0 (0: no limit)");
-  if (t->kick_every > 0) {
-    if (t->kick_phase < 0 || t->kick_phase >= t->kick_every)
-      return fail(HS_E_ARG, "kick_phase must lie in [0, kick_every)");
-    if (!t->kick_dv) return fail(HS_E_ARG, "kick_dv is required when kick_every > 0");
-  }
+  if ((rc = trial_extras_check(*t)) != HS_OK) return rc;
   if (nothing) return HS_OK;
   if (!t->state) return fail(HS_E_ARG, "the trial state array is required");
-  const hs_topo* d = nullptr;
-  const hs_simtopo* ds = nullptr;
-  const hs_simtopo_t<float>* dsf = nullptr;
-  rc = sim_device_state(m, &d, &ds, a->precision == HS_PREC_F32 ? &dsf : nullptr);
+  const hs::sim_dev dv = sim_dev_of(m, a->precision, &rc);
   if (rc != HS_OK) return rc;
   hs_sim_trial_args c = *t;
   if (c.sim.n_t < 1) c.sim.n_t = 1;
   if (!c.kick_dv) c.kick_every = 0;  // NULL means no kicks
-  int e = hs::launch_sim_trial(d, ds, dsf, m->sim, c);
-  if (e != 0) return hip_fail((hipError_t)e, "hs_sim_trial launch");
-  return HS_OK;
+  int e = hs::launch_sim_trial(dv, c);
+  return e ? hip_fail((hipError_t)e, "hs_sim_trial launch") : HS_OK;
 }
 
 int hs_sim_trial_summary(const int32_t* state, int32_t n, hs_trial_summary* out, void* stream) {
@@ -1475,51 +1496,43 @@ int hs_sim_trial_summary(const int32_t* state, int32_t n, hs_trial_summary* out,
 int hs_sim_config(hs_model_t m, int32_t n, const double* body, double* config, int32_t config_stride, int32_t precision,
                   void* stream) {
   if (!m) return fail(HS_E_ARG, "null model");
-  if (n < 0 || n > (1 << 30)) return fail(HS_E_ARG, "bad n");
-  if (precision != HS_PREC_F64 && precision != HS_PREC_F32) return fail(HS_E_ARG, "unknown precision");
+  int rc = count_check(n, "bad n");
+  if (rc != HS_OK) return rc;
+  if ((rc = precision_check(precision)) != HS_OK) return rc;
   if (config_stride < m->host.cfg) return fail(HS_E_ARG, "config_stride < config_dim");
   if (n == 0) return HS_OK;
   if (!body || !config) return fail(HS_E_ARG, "null body or config");
-  const hs_topo* d = nullptr;
-  const hs_simtopo* ds = nullptr;
-  const hs_simtopo_t<float>* dsf = nullptr;
-  int rc = sim_device_state(m, &d, &ds, precision == HS_PREC_F32 ? &dsf : nullptr);
+  const hs::sim_dev dv = sim_dev_of(m, precision, &rc);
   if (rc != HS_OK) return rc;
-  int e = hs::launch_sim_config(d, ds, dsf, n, body, config, config_stride, precision, stream);
-  if (e != 0) return hip_fail((hipError_t)e, "hs_sim_config launch");
-  return HS_OK;
+  int e = hs::launch_sim_config(dv, n, body, config, config_stride, precision, stream);
+  return e ? hip_fail((hipError_t)e, "hs_sim_config launch") : HS_OK;
 }
 
 int hs_sim_track_push(hs_model_t m, int32_t n, const double* config, int32_t config_stride, double dt, double* ders,
                       int32_t precision, void* stream) {
   if (!m) return fail(HS_E_ARG, "null model");
-  if (n < 0 || n > (1 << 30)) return fail(HS_E_ARG, "bad n");
-  if (precision != HS_PREC_F64) return fail(HS_E_ARG, "hs_sim_track_push is double precision only");
+  if (int rc = count_check(n, "bad n"); rc != HS_OK) return rc;
+  if (int rc = precision_check(precision, "hs_sim_track_push is double precision only"); rc != HS_OK) return rc;
   if (config_stride < m->host.cfg) return fail(HS_E_ARG, "config_stride < config_dim");
   if (!(dt > 0)) return fail(HS_E_ARG, "dt must be > 0");
   if (n == 0) return HS_OK;
   if (!config || !ders) return fail(HS_E_ARG, "null config or ders");
   int e = hs::launch_track_push(n, m->host.cfg, config, config_stride, dt, ders, stream);
-  if (e != 0) return hip_fail((hipError_t)e, "hs_sim_track_push launch");
-  return HS_OK;
+  return e ? hip_fail((hipError_t)e, "hs_sim_track_push launch") : HS_OK;
 }
 
 // the checks hs_sim_probe and hs_sim_estimate_B share; *nothing = true for an empty call
 static int probe_args_check(hs_model_t m, const hs_sim_probe_args* a, bool* nothing) {
   *nothing = false;
   if (!m || !a) return fail(HS_E_ARG, "null model or args");
-  if (a->n_rollouts < 0 || a->n_rollouts > (1 << 30)) return fail(HS_E_ARG, "bad n_rollouts");
+  if (int rc = count_check(a->n_rollouts, "bad n_rollouts"); rc != HS_OK) return rc;
   if (a->m < 0) return fail(HS_E_ARG, "m < 0");
   if ((int64_t)a->n_rollouts * a->m > (1 << 30)) return fail(HS_E_ARG, "n_rollouts * m too large");
-  if (a->precision != HS_PREC_F64 && a->precision != HS_PREC_F32) return fail(HS_E_ARG, "unknown precision");
+  if (int rc = precision_check(a->precision); rc != HS_OK) return rc;
   if (!a->body || !a->seed) return fail(HS_E_ARG, "body and seed are required");
   if (a->m > 0 && (!a->dtau || !a->config_out || !a->tau_out))
     return fail(HS_E_ARG, "dtau, config_out and tau_out are required");
-  const hs_sim_params& P = a->params;
-  if (!(P.dt > 0)) return fail(HS_E_ARG, "dt must be > 0");
-  if (P.iterations < 0) return fail(HS_E_ARG, "iterations < 0");
-  if (!(P.mu > 0)) return fail(HS_E_ARG, "mu must be > 0 (the reference uses dInfinity: 3 rows per contact)");
-  if (m->sim.m_max > 9 * HS_NMAX) return fail(HS_E_TOPOLOGY, "too many constraint rows for the simulation kernel");
+  if (int rc = sim_params_check(m, a->params); rc != HS_OK) return rc;
   *nothing = a->n_rollouts == 0 || a->m == 0;
   return HS_OK;
 }
@@ -1527,10 +1540,8 @@ static int probe_args_check(hs_model_t m, const hs_sim_probe_args* a, bool* noth
 // the probe launch; seed_copy: [B] device words the launch may overwrite (the probes read the seeds
 // from it while the last probe of each rollout writes a->seed)
 static int probe_launch(hs_model_t m, const hs_sim_probe_args* a, uint32_t* seed_copy) {
-  const hs_topo* d = nullptr;
-  const hs_simtopo* ds = nullptr;
-  const hs_simtopo_t<float>* dsf = nullptr;
-  int rc = sim_device_state(m, &d, &ds, a->precision == HS_PREC_F32 ? &dsf : nullptr);
+  int rc = HS_OK;
+  const hs::sim_dev dv = sim_dev_of(m, a->precision, &rc);
   if (rc != HS_OK) return rc;
   hipStream_t st = (hipStream_t)a->stream;
   hipError_t e = hipMemcpyAsync(seed_copy, a->seed, (size_t)a->n_rollouts * sizeof(uint32_t), hipMemcpyDeviceToDevice, st);
@@ -1553,9 +1564,8 @@ static int probe_launch(hs_model_t m, const hs_sim_probe_args* a, uint32_t* seed
   k.tau_out = a->tau_out;
   k.body_out = a->body_out;
   k.seed_out = a->seed;
-  int le = hs::launch_sim_probe(d, ds, dsf, m->sim, k);
-  if (le != 0) return hip_fail((hipError_t)le, "hs_sim_probe launch");
-  return HS_OK;
+  int le = hs::launch_sim_probe(dv, k);
+  return le ? hip_fail((hipError_t)le, "hs_sim_probe launch") : HS_OK;
 }
 
 int hs_sim_probe(hs_model_t m, const hs_sim_probe_args* a) {
@@ -1576,9 +1586,9 @@ int hs_sim_probe(hs_model_t m, const hs_sim_probe_args* a) {
 
 static int regress_check(hs_model_t m, int32_t n, int32_t ms, int32_t precision) {
   if (!m) return fail(HS_E_ARG, "null model");
-  if (n < 0 || n > (1 << 30)) return fail(HS_E_ARG, "bad n");
+  if (int rc = count_check(n, "bad n"); rc != HS_OK) return rc;
   if (ms < 0) return fail(HS_E_ARG, "m < 0");
-  if (precision != HS_PREC_F64) return fail(HS_E_ARG, "the regression is double precision only");
+  if (int rc = precision_check(precision, "the regression is double precision only"); rc != HS_OK) return rc;
   if (ms > 0 && ms < m->sim.nmj + 1)
     return fail(HS_E_ARG, "0 < m < nmj + 1: the rank-deficient basic solution is not restated");
   if (ms > 0 && hs::regress_lds_bytes(ms, m->sim.nmj, m->host.cfg) > 64 * 1024)
@@ -1593,8 +1603,7 @@ int hs_sim_regress_B(hs_model_t m, int32_t n, int32_t ms, const double* T, const
   if (n == 0) return HS_OK;
   if (!Bt || !rank || (ms > 0 && (!T || !U))) return fail(HS_E_ARG, "null T, U, Bt or rank");
   int e = hs::launch_regress_B(n, ms, m->sim.nmj, m->host.cfg, T, U, Bt, rank, stream);
-  if (e != 0) return hip_fail((hipError_t)e, "hs_sim_regress_B launch");
-  return HS_OK;
+  return e ? hip_fail((hipError_t)e, "hs_sim_regress_B launch") : HS_OK;
 }
 
 size_t hs_sim_estimate_workspace(hs_model_t m, int32_t n_rollouts, int32_t ms) {
@@ -1655,8 +1664,8 @@ void hs_cpc_default_params(hs_cpc_params* p) {
 // the checks of hs_cpc_torques, apart from its pointers (hs_sim_cpc_step fills those in itself)
 static int cpc_check(hs_model_t m, int32_t n, int32_t n_tp, int32_t precision, const hs_cpc_params& P) {
   if (!m) return fail(HS_E_ARG, "null model");
-  if (n < 0 || n > (1 << 30)) return fail(HS_E_ARG, "bad n_rollouts");
-  if (precision != HS_PREC_F64) return fail(HS_E_ARG, "the CPC controller is double precision only");
+  if (int rc = count_check(n, "bad n_rollouts"); rc != HS_OK) return rc;
+  if (int rc = precision_check(precision, "the CPC controller is double precision only"); rc != HS_OK) return rc;
   if (P.n_cand < 1 || P.n_cand > 64) return fail(HS_E_ARG, "n_cand must lie in 1..64");
   if (n_tp < P.n_cand) return fail(HS_E_ARG, "n_tp < n_cand");
   // the gain loop halves k until k <= kc: it ends for a finite k0 and kc > 0 only
@@ -1673,26 +1682,23 @@ int hs_cpc_torques(hs_model_t m, const hs_cpc_args* a) {
   int rc = cpc_check(m, a->n_rollouts, a->n_tp, a->precision, a->params);
   if (rc != HS_OK) return rc;
   if (a->state_stride < 2 * (int64_t)m->host.cfg) return fail(HS_E_ARG, "state_stride < 2 * config_dim");
-  if (a->tp_stride != 0 && a->tp_stride < (int64_t)a->n_tp * (2 * m->host.cfg + m->sim.nmj))
-    return fail(HS_E_ARG, "tp_stride smaller than one set of target points (0: a shared set)");
+  if ((rc = tp_stride_check(m, a->tp_stride, a->n_tp)) != HS_OK) return rc;
   if (a->n_rollouts == 0) return HS_OK;
   if (!a->Bt || !a->state || !a->tp || !a->low_tpdist || !a->tau || !a->last_tpi || !a->flags)
     return fail(HS_E_ARG, "Bt, state, tp, low_tpdist, tau, last_tpi and flags are required");
   int e = hs::launch_cpc_torques(*a, m->sim.nmj, m->host.cfg);
-  if (e != 0) return hip_fail((hipError_t)e, "hs_cpc_torques launch");
-  return HS_OK;
+  return e ? hip_fail((hipError_t)e, "hs_cpc_torques launch") : HS_OK;
 }
 
 int hs_cpc_target_points(hs_model_t m, int32_t n, int32_t n_t, const double* q_tab, const double* dq_tab,
                          const double* tau_tab, uint32_t mask, double* tp, void* stream) {
   if (!m) return fail(HS_E_ARG, "null model");
-  if (n < 0 || n > (1 << 30)) return fail(HS_E_ARG, "bad n_rollouts");
+  if (int rc = count_check(n, "bad n_rollouts"); rc != HS_OK) return rc;
   if (n_t < 1) return fail(HS_E_ARG, "n_t must be >= 1");
   if (n == 0) return HS_OK;
   if (!q_tab || !dq_tab || !tau_tab || !tp) return fail(HS_E_ARG, "null table or tp");
   int e = hs::launch_cpc_target_points(n, n_t, m->host.cfg, m->sim.nmj, q_tab, dq_tab, tau_tab, mask, tp, stream);
-  if (e != 0) return hip_fail((hipError_t)e, "hs_cpc_target_points launch");
-  return HS_OK;
+  return e ? hip_fail((hipError_t)e, "hs_cpc_target_points launch") : HS_OK;
 }
 
 // the workspace of hs_sim_cpc_step, in doubles: config_out, T, U, Bt, the CPC torques, a copy of the seeds,
@@ -1743,8 +1749,7 @@ int hs_sim_cpc_step(hs_model_t m, const hs_sim_cpc_args* c) {
   if (rc != HS_OK) return rc;
   rc = cpc_check(m, B, c->n_tp, s.precision, c->cpc);
   if (rc != HS_OK) return rc;
-  if (c->tp_stride != 0 && c->tp_stride < (int64_t)c->n_tp * (2 * m->host.cfg + m->sim.nmj))
-    return fail(HS_E_ARG, "tp_stride smaller than one set of target points (0: a shared set)");
+  if ((rc = tp_stride_check(m, c->tp_stride, c->n_tp)) != HS_OK) return rc;
   if (c->dtau_step_stride != 0 && c->dtau_step_stride < (int64_t)B * c->m * m->sim.nmj)
     return fail(HS_E_ARG, "dtau_step_stride smaller than one step's perturbations (0: one set)");
   hs_sim_trial_args tr = c->trial;
@@ -1755,13 +1760,8 @@ int hs_sim_cpc_step(hs_model_t m, const hs_sim_cpc_args* c) {
   tr.sim.tau_tab = (const double*)c->workspace;  // placeholder
   tr.open_loop = 1;
   if (s.n_steps < 0) return fail(HS_E_ARG, "n_steps < 0");
-  {
-    hs_sim_trial_args chk = tr;
-    chk.sim.n_rollouts = chk.sim.n_steps = 0;  // the parameter checks alone
-    if (B > 0 && (!s.body || !s.seed || !s.tsi)) return fail(HS_E_ARG, "body, seed and tsi are required");
-    rc = hs_sim_trial(m, &chk);
-    if (rc != HS_OK) return rc;
-  }
+  if (B > 0 && (!s.body || !s.seed || !s.tsi)) return fail(HS_E_ARG, "body, seed and tsi are required");
+  if ((rc = trial_extras_check(tr)) != HS_OK) return rc;
   if (B == 0 || s.n_steps == 0) return HS_OK;
   if (!c->trial.state) return fail(HS_E_ARG, "the trial state array is required");
   if (!c->tp || !c->ders || !c->tau0 || !c->low_tpdist || !c->last_tpi || !c->flags || !c->rank || (c->m > 0 && !c->dtau))

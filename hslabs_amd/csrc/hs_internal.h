@@ -156,29 +156,35 @@ int launch_fk(const hs_topo* d_topo, int32_t n_parts, int32_t n_cfg, const doubl
 int launch_lik(const hs_topo* d_topo, int32_t n_cfg, const double* rec, int32_t ignore_reach, double* config,
                uint32_t* status, void* stream);
 
-// closed-loop simulation kernels (hs_sim.hip); return hipError_t values
-int launch_sim_reset(const hs_topo* d_topo, const hs_simtopo* d_sim, int32_t n_rollouts, const double* config,
-                     int32_t config_stride, double* body, int32_t precision, void* stream);
-int launch_sim_steps(const hs_topo* d_topo, const hs_simtopo* d_sim, const hs_simtopo_t<float>* d_sim_f32,
-                     const hs_simtopo& host_sim, const hs_sim_args& a);
-// the TRIAL instantiations of the same kernel (hs_sim_trial), and the tally of a state array into
+// What every simulation launcher needs of a model on the current device: the device copies of the topology
+// and of the ODE world, the world rounded for the single-precision kernels (null unless asked for with
+// HS_PREC_F32), and the host's world (the sizes that pick a kernel's LDS class).
+struct sim_dev {
+  const hs_topo* topo;
+  const hs_simtopo* sim;
+  const hs_simtopo_t<float>* sim_f32;
+  const hs_simtopo& host;
+};
+// closed-loop simulation kernels (hs_sim.hip; the kernel itself is hs_sim_kernel.h); return hipError_t values
+int launch_sim_reset(const sim_dev& dv, int32_t n_rollouts, const double* config, int32_t config_stride, double* body,
+                     int32_t precision, void* stream);
+int launch_sim_steps(const sim_dev& dv, const hs_sim_args& a);
+// the TRIAL instantiations of the same kernel (hs_sim_trial.hip), and the tally of a state array into
 // acc = {running, survived, fallen, min fall tsi (INT32_MAX: none), sum fall tsi}, preset by the caller
-int launch_sim_trial(const hs_topo* d_topo, const hs_simtopo* d_sim, const hs_simtopo_t<float>* d_sim_f32,
-                     const hs_simtopo& host_sim, const hs_sim_trial_args& a);
+int launch_sim_trial(const sim_dev& dv, const hs_sim_trial_args& a);
 int launch_trial_summary(const int32_t* state, int32_t n, hs_trial_summary* acc, void* stream);
 // resident rollouts per CU of hs_sim_step's kernels for a model size: {fp64, fp32, fp32 3 waves/SIMD}
 int sim_step_occupancy(int32_t n, int32_t m_max, int32_t* out3);
 // "dynamics from simulation" (hs_sim_probe.hip): the batch get_ode_config, the derivative tracker's
 // push, the PROBE instantiations of the simulation kernel (B * m wavefronts), a probe's acceleration
-// from a copy of the tracker, and the regression of accelerations on torques (fp64). d_sim_f32 is
+// from a copy of the tracker, and the regression of accelerations on torques (fp64). dv.sim_f32 is
 // needed with HS_PREC_F32 only. regress_lds_bytes: the regression's LDS for m samples (the caller
 // rejects more than 64 KB).
-int launch_sim_config(const hs_topo* d_topo, const hs_simtopo* d_sim, const hs_simtopo_t<float>* d_sim_f32, int32_t n,
-                      const double* body, double* config, int32_t config_stride, int32_t precision, void* stream);
+int launch_sim_config(const sim_dev& dv, int32_t n, const double* body, double* config, int32_t config_stride,
+                      int32_t precision, void* stream);
 int launch_track_push(int32_t n, int32_t cfg, const double* config, int32_t config_stride, double dt, double* ders,
                       void* stream);
-int launch_sim_probe(const hs_topo* d_topo, const hs_simtopo* d_sim, const hs_simtopo_t<float>* d_sim_f32,
-                     const hs_simtopo& host_sim, const hs_sim_probe_kargs& a);
+int launch_sim_probe(const sim_dev& dv, const hs_sim_probe_kargs& a);
 int launch_probe_accel(int32_t n, int32_t m, int32_t cfg, const double* config_out, const double* ders, double dt,
                        double* U, void* stream);
 int launch_regress_B(int32_t n, int32_t m, int32_t nmj, int32_t cfg, const double* T, const double* U, double* Bt,

@@ -1,8 +1,13 @@
 // hs_sim_config.h -- visualizer::get_ode_config (visualization.cpp:378-396) on a simulated world: the
-// inverse of hs_sim_reset's pose construction. Included by hs_sim.hip in the probe translation unit
-// (hs_sim_probe.hip), after hinge_angle, inside its anonymous namespace: the probe's tail and
-// hs_sim_config share these functions, so the two agree bitwise on the same body state.
+// inverse of hs_sim_reset's pose construction. Included by hs_sim_kernel.h: the PROBE instantiations' tail
+// and hs_sim_config (hs_sim_probe.hip) share these functions, so the two agree bitwise on the same body
+// state. Like the kernel they are local to the unit that includes them.
 #pragma once
+#include "hs_internal.h"
+#include "hs_math.h"
+#include "hs_ode.h"
+
+namespace {
 
 // A body array [n_parts][HS_SIM_BODY] seen the way hinge_angle reads the kernel's LDS world (s.q[part])
 template <class Real>
@@ -24,7 +29,7 @@ __device__ inline void torso_config(const hs_topo* T, const hs_aff34& body_geom,
   using namespace hsd;
   const double qd[4] = {(double)q[0], (double)q[1], (double)q[2], (double)q[3]};
   double R[12];
-  q_to_R(qd, R);
+  hsode::q_to_R(qd, R);
   A34 A;
   for (int r = 0; r < 3; r++) {
     for (int c = 0; c < 3; c++) A.at(r, c) = R[r * 4 + c];
@@ -43,3 +48,5 @@ __device__ inline void torso_config(const hs_topo* T, const hs_aff34& body_geom,
     out[3 + i] = (IO)ang[i];
   }
 }
+
+}  // namespace

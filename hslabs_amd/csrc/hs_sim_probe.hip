@@ -1,11 +1,10 @@
 // hs_sim_probe.hip -- "dynamics from simulation" (modelplayer::estimate_B_by_regression, player.cpp:548-582)
-// for a batch: the PROBE instantiations of the simulation kernel (hs_sim.hip compiled a third time, apart
-// from hs_sim_step's and hs_sim_trial's so that those stay the code they were), get_ode_config, the
+// for a batch: the PROBE instantiations of the simulation kernel (hs_sim_kernel.h; a unit apart from
+// hs_sim_step's and hs_sim_trial's so that those stay the code they were), get_ode_config, the
 // derivative tracker and the regression of accelerations on torques. Built like hs_sim.hip, with
 // -ffp-contract=off: the probes must step exactly as hs_sim_trial steps, and the tracker's
 // subtract-then-scale (odestate.cpp:114-116) must not fuse.
-#define HS_SIM_PROBE_TU 1
-#include "hs_sim.hip"
+#include "hs_sim_kernel.h"
 
 #include <cfloat>
 
@@ -110,43 +109,31 @@ __global__ __launch_bounds__(WAVE) void hs_regress_kernel(int32_t n_rollouts, in
   if (lane == 0) rank[b] = np;
 }
 
-// the fp64 probe kernel is held to the 2-waves/SIMD budget, like the trial kernel
-template <int NM, int MM, class R, class S>
-static void launch_probe_class(const hs_topo* d_topo, const S* d_sim, const hs_sim_probe_kargs& ka, hipStream_t st) {
-  constexpr int MINW = sizeof(R) == 8 ? 2 : 1;
-  hipLaunchKernelGGL((hs_sim_kernel<NM, MM, R, MINW, false, true>), dim3(ka.sim.n_rollouts * ka.m), dim3(WAVE), 0, st,
-                     d_topo, d_sim, ka);
-}
-
+// one wavefront per probe; the fp64 probe kernel is held to the 2-waves/SIMD budget, like the trial kernel
 template <class R, class S>
-static int launch_probe_typed(const hs_topo* d_topo, const S* d_sim, const hs_simtopo& hs, const hs_sim_probe_kargs& ka) {
-  hipStream_t st = (hipStream_t)ka.sim.stream;
-  // the LDS classes of hs_sim_step
-  if (hs.n <= 18 && hs.m_max <= 144)
-    launch_probe_class<18, 144, R>(d_topo, d_sim, ka, st);
-  else if (hs.n <= 22 && hs.m_max <= 176)
-    launch_probe_class<22, 176, R>(d_topo, d_sim, ka, st);
-  else if (hs.n <= HS_NMAX && hs.m_max <= 9 * HS_NMAX)
-    launch_probe_class<HS_NMAX, 9 * HS_NMAX, R>(d_topo, d_sim, ka, st);
-  else
-    return (int)hipErrorInvalidValue;
-  return (int)hipGetLastError();
+int launch_probe_typed(const hs_topo* d_topo, const S* d_sim, const hs_simtopo& hs, const hs_sim_probe_kargs& ka) {
+  const bool fits = sim_lds_class(hs.n, hs.m_max, [&](auto nm, auto mm) {
+    constexpr int MINW = sizeof(R) == 8 ? 2 : 1;
+    hipLaunchKernelGGL((hs_sim_kernel<decltype(nm)::value, decltype(mm)::value, R, MINW, false, true>),
+                       dim3(ka.sim.n_rollouts * ka.m), dim3(WAVE), 0, (hipStream_t)ka.sim.stream, d_topo, d_sim, ka);
+  });
+  return fits ? (int)hipGetLastError() : (int)hipErrorInvalidValue;
 }
 
 }  // namespace
 
 namespace hs {
 
-int launch_sim_config(const hs_topo* d_topo, const hs_simtopo* d_sim, const hs_simtopo_t<float>* d_sim_f32, int32_t n,
-                      const double* body, double* config, int32_t config_stride, int32_t precision, void* stream) {
+int launch_sim_config(const sim_dev& dv, int32_t n, const double* body, double* config, int32_t config_stride,
+                      int32_t precision, void* stream) {
   if (n <= 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((n + WAVE - 1) / WAVE);
   if (precision == HS_PREC_F32)
-    hipLaunchKernelGGL(hs_sim_config_kernel<float>, grid, dim3(WAVE), 0, st, d_topo, d_sim_f32, n,
+    hipLaunchKernelGGL(hs_sim_config_kernel<float>, grid, dim3(WAVE), 0, st, dv.topo, dv.sim_f32, n,
                        reinterpret_cast<const float*>(body), reinterpret_cast<float*>(config), config_stride);
   else
-    hipLaunchKernelGGL(hs_sim_config_kernel<double>, grid, dim3(WAVE), 0, st, d_topo, d_sim, n, body, config,
+    hipLaunchKernelGGL(hs_sim_config_kernel<double>, grid, dim3(WAVE), 0, st, dv.topo, dv.sim, n, body, config,
                        config_stride);
   return (int)hipGetLastError();
 }
@@ -160,11 +147,10 @@ int launch_track_push(int32_t n, int32_t cfg, const double* config, int32_t conf
   return (int)hipGetLastError();
 }
 
-int launch_sim_probe(const hs_topo* d_topo, const hs_simtopo* d_sim, const hs_simtopo_t<float>* d_sim_f32,
-                     const hs_simtopo& hs, const hs_sim_probe_kargs& a) {
+int launch_sim_probe(const sim_dev& dv, const hs_sim_probe_kargs& a) {
   if (a.sim.n_rollouts <= 0 || a.m <= 0) return 0;
-  if (a.sim.precision == HS_PREC_F32) return launch_probe_typed<float>(d_topo, d_sim_f32, hs, a);
-  return launch_probe_typed<double>(d_topo, d_sim, hs, a);
+  if (a.sim.precision == HS_PREC_F32) return launch_probe_typed<float>(dv.topo, dv.sim_f32, dv.host, a);
+  return launch_probe_typed<double>(dv.topo, dv.sim, dv.host, a);
 }
 
 int launch_probe_accel(int32_t n, int32_t m, int32_t cfg, const double* config_out, const double* ders, double dt,

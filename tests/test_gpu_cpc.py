@@ -9,15 +9,12 @@ fixtures' cond 1.7, the rest is slack for the sums' order. Measured maxima are p
 t0 / s 4.9e-15, torques 2.9e-14 over the 138 runs of the sweep, 0.0 on the path, and 0.11 of the cond-scaled
 bound on the estimated Bt of the closed-loop test (cond(B_chi) 25 to 346).
 """
-import os
-
 import numpy as np
 import pytest
 
-from conftest import MODELS, PGS_CONFIG
+from sim_gpu_kit import NEVER, copy_state, gpu, models, moved64, new_batch  # noqa: F401
 from test_cpc_reference import (DIMS, FLAG_NONFINITE, MARGIN, NOISE, check_argument_cases, cpc_reference, make_fixture,
                                 sweep)
-from test_gpu_sim_dynamics import NEVER, copy_state, moved, new_batch
 from test_sim_dynamics import CASES
 
 pytestmark = pytest.mark.gpu
@@ -29,31 +26,12 @@ DIAG = dict(loss=True, cand_tpi=True, cand_t0s=True, passes=True, i_best=True)
 
 
 @pytest.fixture(scope="module")
-def gpu(product):
-    import torch
-
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return product
-
-
-@pytest.fixture(scope="module")
-def models(gpu):
-    return {name: (gpu.KinematicModel(os.path.join(MODELS, f"{name}.xml")), gpu.read_pgs_config(PGS_CONFIG, pid))
-            for name, pid in CASES.items()}
-
-
-@pytest.fixture(scope="module")
 def batches(gpu, models):
     """name -> a batch of NB rollouts, used only as the controller's handle (its own state is not read)"""
     res = {name: new_batch(gpu, models, name, n=NB) for name in CASES}
     for name, sb in res.items():
         assert (sb.model.config_dim, sb.model.nmj) == DIMS[name]
     return res
-
-
-@pytest.fixture(scope="module")
-def moved64(gpu, models):
-    return {name: moved(gpu, models, name) for name in CASES}
 
 
 def run_cpc(sb, fx, rollouts, tp=None, low=1, per_rollout_tp=False, **params):

@@ -15,33 +15,9 @@ import numpy as np
 import pytest
 
 from conftest import MODELS
+from sim_gpu_kit import BODY_TOL, gpu, hmodels, make_batch, tables  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-BODY_TOL = 1e-10
-
-
-@pytest.fixture(scope="module")
-def gpu(product):
-    import torch
-
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return product
-
-
-@pytest.fixture(scope="module")
-def hmodels(gpu):
-    return {n: gpu.KinematicModel(os.path.join(MODELS, f"{n}.xml")) for n in ("hexapod", "spider", "myant")}
-
-
-def tables(sb):
-    return sb.tables.q.cpu().numpy(), sb.tables.dq.cpu().numpy(), sb.tables.tau.cpu().numpy()
-
-
-def make_batch(gpu, model, name, B, period=3.0, **kw):
-    from hslabs_amd import synth
-
-    return gpu.SimBatch(model, synth.gen_sim_params(B, name, period=period), **kw)
 
 
 @pytest.mark.parametrize("name", ["hexapod", "spider", "myant"])

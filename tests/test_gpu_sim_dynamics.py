@@ -8,85 +8,17 @@ which have a tracker history and other contact sets -- of the hexapod (pgs id 8)
 Bounds are those of tests/test_gpu_sim.py and tests/test_gpu_sim_trial.py: bodies 1e-10 (BODY_TOL),
 hinge angles 1e-9; the configuration round trip has tests/test_gpu_config.py's 1e-12.
 """
-import os
-
 import numpy as np
 import pytest
 
-from conftest import MODELS, PGS_CONFIG
+from sim_gpu_kit import (BODY_TOL, NEVER, copy_state, gpu, models, moved, moved64, new_batch)  # noqa: F401
 from test_sim_dynamics import CASES, MOVE_STEPS, TSI0, lstsq_Bt, np_probe_accel, np_track_push, oracle_probes
 
 pytestmark = pytest.mark.gpu
 
-BODY_TOL = 1e-10
 Q_TOL = 1e-9
 CFG_TOL = 1e-12
 B = len(MOVE_STEPS)
-NEVER = 10 ** 6
-
-
-@pytest.fixture(scope="module")
-def gpu(product):
-    import torch
-
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return product
-
-
-@pytest.fixture(scope="module")
-def models(gpu):
-    return {name: (gpu.KinematicModel(os.path.join(MODELS, f"{name}.xml")), gpu.read_pgs_config(PGS_CONFIG, pid))
-            for name, pid in CASES.items()}
-
-
-def new_batch(gpu, models, name, dtype=None, n=B):
-    m, p = models[name]
-    return gpu.SimBatch(m, [p] * n, tsi0=TSI0, dtype=dtype)
-
-
-def moved(gpu, models, name, dtype=None):
-    """A batch whose rollout i has taken MOVE_STEPS[i] position-control steps, the tracker pushed before
-    every one of them (float64), and the last torques of each rollout. Returns (batch, tau0, history)
-    with history = the bodies before each of the 25 steps [25][B][n][13]."""
-    import torch
-
-    sb = new_batch(gpu, models, name, dtype)
-    f64 = sb.dtype == torch.float64
-    nmj = sb.model.nmj
-
-    def snap(tau):
-        return sb.body.clone(), sb.seed.clone(), sb.tsi.clone(), sb.ders.clone(), tau
-
-    snaps, hist = {0: snap(torch.zeros((B, nmj), dtype=sb.dtype, device=sb.device))}, []
-    for i in range(max(MOVE_STEPS)):
-        hist.append(sb.body.clone())
-        if f64:
-            sb.track_push()
-        o = sb.step(1, outputs=("tau_cmd",))
-        if i + 1 in MOVE_STEPS:
-            snaps[i + 1] = snap(o["tau_cmd"][:, -1].clone())
-    tau0 = torch.empty((B, nmj), dtype=sb.dtype, device=sb.device)
-    for i, n in enumerate(MOVE_STEPS):
-        body, seed, tsi, ders, tau = snaps[n]
-        sb.body[i], sb.seed[i], sb.tsi[i], sb.ders[i], tau0[i] = body[i], seed[i], tsi[i], ders[i], tau[i]
-    sb.last_tau = tau0
-    torch.cuda.synchronize()
-    return sb, tau0, torch.stack(hist)
-
-
-@pytest.fixture(scope="module")
-def moved64(gpu, models):
-    """name -> (batch, tau0, history); read only: tests copy what they advance"""
-    return {name: moved(gpu, models, name) for name in CASES}
-
-
-def copy_state(dst, src):
-    dst.body.copy_(src.body)
-    dst.seed.copy_(src.seed)
-    dst.tsi.copy_(src.tsi)
-    dst.ders.copy_(src.ders)
-    dst.last_tau = None if src.last_tau is None else src.last_tau.clone()
-    return dst
 
 
 def sequential_probes(seq, tau):

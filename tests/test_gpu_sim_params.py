@@ -1,4 +1,4 @@
-"""GPU parity of the simulation kernel (hs_sim.hip: hs_sim_step, and the TRIAL and PROBE instantiations
+"""GPU parity of the simulation kernel (hs_sim_kernel.h: hs_sim_step, and the TRIAL and PROBE instantiations
 hs_sim_trial and hs_sim_probe) with the oracle under every parameter set of tests/test_sim_params.py:
 each field of hs_sim_params away from its default, on the scenarios of that file (stand, land, sunk).
 
@@ -10,7 +10,7 @@ rounding-sized perturbation does over the same steps (1.1e-13 at most).
 
 What these tests found: sor_pair bounded a contact's normal row above by mu (the friction rows' bound;
 the oracle and ODE leave the normal row in [0, inf)). With the default mu = inf nothing showed; under
-mu = 0.5 the hexapod's contact counts left the oracle's at the third step. Fixed in hs_sim.hip.
+mu = 0.5 the hexapod's contact counts left the oracle's at the third step. Fixed there.
 
 Measured on MI355X (library 1edc3706), maxima over the rollouts of each case; no run was shortened:
   a. 12 steps, B = 4 (2 stand, 2 land), hexapod / myant, spider for mu=0.5, iterations=9, mixed:
@@ -30,8 +30,9 @@ import numpy as np
 import pytest
 
 from conftest import MODELS
+from sim_gpu_kit import BODY_TOL, NEVER, gpu, hmodels, host, tables  # noqa: F401
 from test_sim_dynamics import oracle_probes
-from test_sim_params import (BODY_TOL, F32_D_OTHER, F32_ROLLOUTS, KICK_DV, KICK_EVERY, KICK_PHASE, PARAM_SETS,
+from test_sim_params import (F32_D_OTHER, F32_ROLLOUTS, KICK_DV, KICK_EVERY, KICK_PHASE, PARAM_SETS,
                              STAND_ONLY, STEPS, SUNK_SETS, TSI0, oracle_kicked, scenario, scenario_of, set_n_t,
                              torso_distance)
 
@@ -41,20 +42,6 @@ B_STEP = 4
 SPIDER_SETS = ("mu=0.5", "iterations=9", "mixed")
 STEP_CASES = [(p, m) for p in PARAM_SETS for m in ("hexapod", "myant")] + [(p, "spider") for p in SPIDER_SETS]
 SUNK_CASES = [(p, m) for p in SUNK_SETS for m in ("hexapod", "myant")] + [("mu=0.5", "spider"), ("mixed", "spider")]
-NEVER = 10 ** 6
-
-
-@pytest.fixture(scope="module")
-def gpu(product):
-    import torch
-
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return product
-
-
-@pytest.fixture(scope="module")
-def hmodels(gpu):
-    return {n: gpu.KinematicModel(os.path.join(MODELS, f"{n}.xml")) for n in ("hexapod", "spider", "myant")}
 
 
 def set_batch(gpu, hmodels, name, B, pname, **kw):
@@ -82,14 +69,6 @@ def start(sb, whiches):
     sb.body.copy_(torch.as_tensor(body, device=sb.device))
     torch.cuda.synchronize()
     return sb.body.cpu().numpy().astype(np.float64)
-
-
-def tables(sb):
-    return [t.cpu().numpy().astype(np.float64) for t in (sb.tables.q, sb.tables.dq, sb.tables.tau)]
-
-
-def host(out):
-    return {k: v.cpu().numpy() for k, v in out.items()}
 
 
 def oracle_params(O, pname, **kw):

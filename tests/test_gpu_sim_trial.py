@@ -14,22 +14,14 @@ import numpy as np
 import pytest
 
 from conftest import MODELS, PGS_CONFIG
+from sim_gpu_kit import BODY_TOL, batch, gpu, host  # noqa: F401
 from test_sim_trial import (HC, KICK_D, KICK_EVERY, KICK_PHASE, KICK_STEPS, LIMIT_STEPS, LIMITS, N_T, RUNNING,
                             SURVIVED, TSI0, assert_kick_margins, assert_limit_margins, kick_traces, limit_traces,
                             oracle_trial)
 
 pytestmark = pytest.mark.gpu
 
-BODY_TOL = 1e-10  # tests/test_gpu_sim.py
 KICK_ARGS = dict(kick_every=KICK_EVERY, kick_phase=KICK_PHASE, hc=HC, check_from=0, check_until=-1)
-
-
-@pytest.fixture(scope="module")
-def gpu(product):
-    import torch
-
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return product
 
 
 @pytest.fixture(scope="module")
@@ -42,18 +34,10 @@ def pgs8(gpu):
     return gpu.read_pgs_config(PGS_CONFIG, 8)
 
 
-def batch(gpu, model, p, B, **kw):
-    return gpu.SimBatch(model, [p] * B, tsi0=TSI0, **kw)
-
-
 def kick_dv(ds=KICK_D):
     dv = np.zeros((len(ds), 3))
     dv[:, 1] = ds
     return dv
-
-
-def host(out):
-    return {k: v.cpu().numpy() for k, v in out.items()}
 
 
 @pytest.fixture(scope="module")

@@ -36,8 +36,7 @@ from conftest import MODELS, record_to_oracle_gait
 
 STEPS = 12
 TSI0 = 2
-BODY_TOL = 1e-10       # tests/test_gpu_sim.py
-FELT = 1e-6            # 1e4 * BODY_TOL
+FELT = 1e-6            # 1e4 * BODY_TOL (tests/sim_gpu_kit.py)
 SENS_TOL = 1e-12       # BODY_TOL / 100
 F32_D_OTHER = 1e-2     # a set discriminates in fp32 when it moves the torso by more than this
 F32_MIN_SETS = 12
