@@ -18,7 +18,13 @@ the exception, built with
 stance feet, so it keeps the oracle's unfused rounding (a per-file flag).
 So is hs_config.hip (the per-configuration FK / IK of the model.h API), which is
 not on the hot path and keeps the reference's rounding.
-Sources compile to objects in parallel, then link.
+The step kernels are two units, hs_kernels.hip (fp64, with what exists once: the pergen record kernel and
+the diagnostic builds' readers) and hs_kernels_f32.hip (fp32), over the same headers: hs_step_base.h (constants,
+LDS layouts, workspaces), hs_step_kin.h (gait setup, sampler, kinematics, dynamics), hs_step_solve.h (the
+solves), hs_rollout_kernel.h (hs_rollout_kernel, hs_prep_kernel and their launchers) and hs_limb.h (the
+limb-lane kernel and its launcher).
+Sources compile to objects in parallel, then link; the library is rebuilt when a source or any header of
+csrc/ is newer than it.
 """
 from __future__ import annotations
 
@@ -38,7 +44,6 @@ SOURCES = ["hs_kernels.hip", "hs_kernels_f32.hip", "hs_sim.hip", "hs_sim_trial.h
 # (same SONAME) is the one bound
 LIBS = ["-L/opt/rocm/lib", "-lrccl"]
 VARIANT_DIR = os.path.join(OUT_DIR, "variants")
-HEADERS = ["hs_topo.h", "hs_simtopo.h", "hs_ode.h", "hs_math.h", "hs_internal.h", "hs_sim_kernel.h", "hs_sim_config.h", "hs_limb.h", "hs_limb_tile.h", "hs_colpiv.h", os.path.join("..", "..", "include", "hslabs.h")]
 ARCH = os.environ.get("HSLABS_ARCH", "gfx950")
 # per-source FMA contraction (default: fast, except where a `#pragma clang fp contract(off)` says not)
 CONTRACT = {"hs_sim.hip": "off", "hs_sim_trial.hip": "off", "hs_sim_probe.hip": "off", "hs_cpc.hip": "off", "hs_config.hip": "off"}
@@ -56,11 +61,23 @@ def _hipcc() -> str:
     raise RuntimeError("hipcc not found (ROCm 7.x required)")
 
 
+def _headers() -> list:
+    """What the staleness check watches besides SOURCES: every header of csrc/ and the public ABI header, listed
+    when asked (paths relative to csrc/), so that a new header cannot be left out and a stale library reused."""
+    return sorted(f for f in os.listdir(SRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "hslabs.h")]
+
+
+def __getattr__(name: str):
+    if name == "HEADERS":  # build.HEADERS: the list as of this access
+        return _headers()
+    raise AttributeError(name)
+
+
 def _stale() -> bool:
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(SRC, f) for f in SOURCES + HEADERS]
+    deps = [os.path.join(SRC, f) for f in SOURCES + _headers()]
     return any(os.path.getmtime(d) > t for d in deps if os.path.exists(d))
 
 

@@ -1008,6 +1008,42 @@ int hs_run_mixed_calls(hs_mixed_t p, const hs_run_args* a, int32_t n_calls) {
   return run_fused(cx, r, n_calls, route(cx, r, run_entry::CALLS));
 }
 
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// host-array entry points: a synchronous call on host arrays allocates device buffers, uploads its inputs,
+// runs its device twin, downloads the outputs and frees
+// ---------------------------------------------------------------------------
+namespace {
+
+// Device scratch of such a call, freed on scope exit. Every operation takes the call's first error and does
+// nothing once there is one, so a call lists its buffers and tests `e` once per message.
+struct dev_buf {
+  void* p = nullptr;
+  ~dev_buf() { (void)hipFree(p); }
+  template <class T>
+  T* as() const { return static_cast<T*>(p); }
+  // an output: n elements
+  template <class T>
+  void alloc(hipError_t& e, size_t n) {
+    if (e == hipSuccess && n) e = hipMalloc(&p, n * sizeof(T));
+  }
+  // an input: allocated and filled from the host's n elements
+  template <class T>
+  void upload(hipError_t& e, const T* host, size_t n) {
+    alloc<T>(e, n);
+    if (e == hipSuccess && n) e = hipMemcpy(p, host, n * sizeof(T), hipMemcpyHostToDevice);
+  }
+  // host may be null: an output the caller did not ask for
+  template <class T>
+  void download(hipError_t& e, T* host, size_t n) const {
+    if (e == hipSuccess && host && n) e = hipMemcpy(host, p, n * sizeof(T), hipMemcpyDeviceToHost);
+  }
+};
+
+}  // namespace
+
+extern "C" {
 
 int hs_complete_traj(hs_model_t m, const hs_gait_params* params, int32_t B, int32_t n_t, int32_t ignore_reach,
                      double* rec) {
@@ -1015,53 +1051,42 @@ int hs_complete_traj(hs_model_t m, const hs_gait_params* params, int32_t B, int3
   if (B <= 0 || n_t < 2) return fail(HS_E_ARG, "empty batch or n_t < 2");
   const hs_topo& t = m->host;
   const size_t rows = (size_t)B * n_t, cfg = (size_t)t.cfg, nmj = (size_t)t.nmj;
-  hs_gait_params* dp = nullptr;
-  double *dq = nullptr, *ddq = nullptr, *dtau = nullptr;
-  hipError_t e = hipMalloc(&dp, (size_t)B * sizeof(hs_gait_params));
-  if (e == hipSuccess) e = hipMalloc(&dq, rows * cfg * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc(&ddq, rows * cfg * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc(&dtau, rows * nmj * sizeof(double));
-  if (e == hipSuccess) e = hipMemcpy(dp, params, (size_t)B * sizeof(hs_gait_params), hipMemcpyHostToDevice);
-  int rc = HS_OK;
-  if (e != hipSuccess) {
-    rc = hip_fail(e, "alloc/copy");
-  } else {
-    hs_run_args a;
-    memset(&a, 0, sizeof(a));
-    a.n_rollouts = B;
-    a.horizon = n_t;  // compute_torques_over_period: steps i = 2 .. n_t + 1
-    a.n_t = n_t;
-    a.ignore_reach = ignore_reach;
-    a.params = dp;
-    a.q = dq;
-    a.dq = ddq;
-    a.tau = dtau;
-    rc = hs_run(m, &a);
-    std::vector<double> q(rows * cfg), v(rows * cfg), tau(rows * nmj);
-    if (rc == HS_OK) e = hipDeviceSynchronize();
-    if (rc == HS_OK && e == hipSuccess) e = hipMemcpy(q.data(), dq, q.size() * sizeof(double), hipMemcpyDeviceToHost);
-    if (rc == HS_OK && e == hipSuccess) e = hipMemcpy(v.data(), ddq, v.size() * sizeof(double), hipMemcpyDeviceToHost);
-    if (rc == HS_OK && e == hipSuccess)
-      e = hipMemcpy(tau.data(), dtau, tau.size() * sizeof(double), hipMemcpyDeviceToHost);
-    if (rc == HS_OK && e != hipSuccess) rc = hip_fail(e, "run/copy back");
-    if (rc == HS_OK) {
-      const size_t len = 2 * cfg + nmj;
-      for (int32_t b = 0; b < B; b++)
-        for (int32_t tsi = 0; tsi < n_t; tsi++) {  // get_complete_traj_rec: tsi < 2 -> tsi + n_t
-          const int32_t i = (tsi < 2) ? tsi + n_t : tsi;
-          const size_t src = (size_t)b * n_t + (size_t)(i - 2);
-          double* r = rec + ((size_t)b * n_t + tsi) * len;
-          std::copy(&q[src * cfg], &q[src * cfg] + cfg, r);
-          std::copy(&v[src * cfg], &v[src * cfg] + cfg, r + cfg);
-          std::copy(&tau[src * nmj], &tau[src * nmj] + nmj, r + 2 * cfg);
-        }
+  dev_buf dp, dq, ddq, dtau;
+  hipError_t e = hipSuccess;
+  dp.upload(e, params, (size_t)B);
+  dq.alloc<double>(e, rows * cfg);
+  ddq.alloc<double>(e, rows * cfg);
+  dtau.alloc<double>(e, rows * nmj);
+  if (e != hipSuccess) return hip_fail(e, "alloc/copy");
+  hs_run_args a;
+  memset(&a, 0, sizeof(a));
+  a.n_rollouts = B;
+  a.horizon = n_t;  // compute_torques_over_period: steps i = 2 .. n_t + 1
+  a.n_t = n_t;
+  a.ignore_reach = ignore_reach;
+  a.params = dp.as<hs_gait_params>();
+  a.q = dq.as<double>();
+  a.dq = ddq.as<double>();
+  a.tau = dtau.as<double>();
+  const int rc = hs_run(m, &a);
+  if (rc != HS_OK) return rc;
+  std::vector<double> q(rows * cfg), v(rows * cfg), tau(rows * nmj);
+  e = hipDeviceSynchronize();
+  dq.download(e, q.data(), q.size());
+  ddq.download(e, v.data(), v.size());
+  dtau.download(e, tau.data(), tau.size());
+  if (e != hipSuccess) return hip_fail(e, "run/copy back");
+  const size_t len = 2 * cfg + nmj;
+  for (int32_t b = 0; b < B; b++)
+    for (int32_t tsi = 0; tsi < n_t; tsi++) {  // get_complete_traj_rec: tsi < 2 -> tsi + n_t
+      const int32_t i = (tsi < 2) ? tsi + n_t : tsi;
+      const size_t src = (size_t)b * n_t + (size_t)(i - 2);
+      double* r = rec + ((size_t)b * n_t + tsi) * len;
+      std::copy(&q[src * cfg], &q[src * cfg] + cfg, r);
+      std::copy(&v[src * cfg], &v[src * cfg] + cfg, r + cfg);
+      std::copy(&tau[src * nmj], &tau[src * nmj] + nmj, r + 2 * cfg);
     }
-  }
-  (void)hipFree(dp);
-  (void)hipFree(dq);
-  (void)hipFree(ddq);
-  (void)hipFree(dtau);
-  return rc;
+  return HS_OK;
 }
 
 int hs_run_forces_host(hs_model_t m, const hs_gait_params* params, int32_t B, int32_t n_t, int32_t k0, int32_t H,
@@ -1070,41 +1095,29 @@ int hs_run_forces_host(hs_model_t m, const hs_gait_params* params, int32_t B, in
   if (B <= 0 || H <= 0) return fail(HS_E_ARG, "empty batch");
   const hs_topo& t = m->host;
   const size_t rows = (size_t)B * H, nmj = (size_t)t.nmj, ncf = 3 * (size_t)t.nf;
-  hs_gait_params* dp = nullptr;
-  double *dtau = nullptr, *dcf = nullptr;
-  uint32_t* dfl = nullptr;
-  hipError_t e = hipMalloc(&dp, (size_t)B * sizeof(hs_gait_params));
-  if (e == hipSuccess) e = hipMalloc(&dtau, rows * nmj * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc(&dcf, rows * ncf * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc(&dfl, rows * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMemcpy(dp, params, (size_t)B * sizeof(hs_gait_params), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dtau, tau_in, rows * nmj * sizeof(double), hipMemcpyHostToDevice);
-  int rc = HS_OK;
-  if (e != hipSuccess) {
-    rc = hip_fail(e, "alloc/copy");
-  } else {
-    hs_run_args a;
-    memset(&a, 0, sizeof(a));
-    a.n_rollouts = B;
-    a.horizon = H;
-    a.k0 = k0;
-    a.n_t = n_t;
-    a.ignore_reach = ignore_reach;
-    a.params = dp;
-    a.cf = dcf;
-    a.flags = dfl;
-    rc = hs_run_forces(m, &a, dtau);
-    if (rc == HS_OK) e = hipDeviceSynchronize();
-    if (rc == HS_OK && e == hipSuccess && cf) e = hipMemcpy(cf, dcf, rows * ncf * sizeof(double), hipMemcpyDeviceToHost);
-    if (rc == HS_OK && e == hipSuccess && flags)
-      e = hipMemcpy(flags, dfl, rows * sizeof(uint32_t), hipMemcpyDeviceToHost);
-    if (rc == HS_OK && e != hipSuccess) rc = hip_fail(e, "run/copy back");
-  }
-  (void)hipFree(dp);
-  (void)hipFree(dtau);
-  (void)hipFree(dcf);
-  (void)hipFree(dfl);
-  return rc;
+  dev_buf dp, dtau, dcf, dfl;
+  hipError_t e = hipSuccess;
+  dp.upload(e, params, (size_t)B);
+  dtau.upload(e, tau_in, rows * nmj);
+  dcf.alloc<double>(e, rows * ncf);
+  dfl.alloc<uint32_t>(e, rows);
+  if (e != hipSuccess) return hip_fail(e, "alloc/copy");
+  hs_run_args a;
+  memset(&a, 0, sizeof(a));
+  a.n_rollouts = B;
+  a.horizon = H;
+  a.k0 = k0;
+  a.n_t = n_t;
+  a.ignore_reach = ignore_reach;
+  a.params = dp.as<hs_gait_params>();
+  a.cf = dcf.as<double>();
+  a.flags = dfl.as<uint32_t>();
+  const int rc = hs_run_forces(m, &a, dtau.as<double>());
+  if (rc != HS_OK) return rc;
+  e = hipDeviceSynchronize();
+  dcf.download(e, cf, rows * ncf);
+  dfl.download(e, flags, rows);
+  return e == hipSuccess ? HS_OK : hip_fail(e, "run/copy back");
 }
 
 int hs_traj_save(const char* path, const double* rec, int32_t n_rows, int32_t rec_len, int32_t append) {
@@ -1127,91 +1140,85 @@ int hs_run_host(hs_model_t m, const hs_gait_params* params, int32_t B, int32_t n
   if (!m || (B > 0 && !params)) return fail(HS_E_ARG, "null argument");
   if (B <= 0 || H <= 0) return fail(HS_E_ARG, "empty batch");
   const hs_topo& t = m->host;
-  size_t nq = (size_t)B * H * t.cfg, ntau = (size_t)B * H * t.nmj, ncf = (size_t)B * H * 3 * t.nf;
-  size_t nx = (size_t)B * H * 6 * t.n, nfl = (size_t)B * H, nwc = (size_t)B * 2;
-  hs_gait_params* dp = nullptr;
-  double *dq = nullptr, *dtau = nullptr, *dcf = nullptr, *dx = nullptr, *dwc = nullptr;
-  uint32_t* dfl = nullptr;
+  const size_t nq = (size_t)B * H * t.cfg, ntau = (size_t)B * H * t.nmj, ncf = (size_t)B * H * 3 * t.nf;
+  const size_t nx = (size_t)B * H * 6 * t.n, nfl = (size_t)B * H, nwc = (size_t)B * 2;
+  dev_buf dp, dq, dtau, dcf, dx, dfl, dwc;  // an output the caller did not ask for stays null on the device too
   hipError_t e = hipSuccess;
-  int rc = HS_OK;
-#define HS_ALLOC(ptr, n, T)                                   \
-  if (e == hipSuccess) e = hipMalloc(&ptr, (n) * sizeof(T));
-  HS_ALLOC(dp, (size_t)B, hs_gait_params);
-  if (q) HS_ALLOC(dq, nq, double);
-  if (tau) HS_ALLOC(dtau, ntau, double);
-  if (cf) HS_ALLOC(dcf, ncf, double);
-  if (x) HS_ALLOC(dx, nx, double);
-  if (flags) HS_ALLOC(dfl, nfl, uint32_t);
-  if (work_cot) HS_ALLOC(dwc, nwc, double);
-#undef HS_ALLOC
-  if (e == hipSuccess) e = hipMemcpy(dp, params, (size_t)B * sizeof(hs_gait_params), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    rc = hip_fail(e, "alloc/copy");
-  } else {
-    hs_run_args a;
-    memset(&a, 0, sizeof(a));
-    a.n_rollouts = B;
-    a.horizon = H;
-    a.k0 = k0;
-    a.n_t = n_t;
-    a.ignore_reach = ignore_reach;
-    a.params = dp;
-    a.q = dq;
-    a.tau = dtau;
-    a.cf = dcf;
-    a.x = dx;
-    a.flags = dfl;
-    a.work_cot = dwc;
-    rc = hs_run(m, &a);
-    if (rc == HS_OK) {
-      e = hipDeviceSynchronize();
-      if (e == hipSuccess && q) e = hipMemcpy(q, dq, nq * sizeof(double), hipMemcpyDeviceToHost);
-      if (e == hipSuccess && tau) e = hipMemcpy(tau, dtau, ntau * sizeof(double), hipMemcpyDeviceToHost);
-      if (e == hipSuccess && cf) e = hipMemcpy(cf, dcf, ncf * sizeof(double), hipMemcpyDeviceToHost);
-      if (e == hipSuccess && x) e = hipMemcpy(x, dx, nx * sizeof(double), hipMemcpyDeviceToHost);
-      if (e == hipSuccess && flags) e = hipMemcpy(flags, dfl, nfl * sizeof(uint32_t), hipMemcpyDeviceToHost);
-      if (e == hipSuccess && work_cot) e = hipMemcpy(work_cot, dwc, nwc * sizeof(double), hipMemcpyDeviceToHost);
-      if (e != hipSuccess) rc = hip_fail(e, "run/copy back");
-    }
-  }
-  (void)hipFree(dp);
-  (void)hipFree(dq);
-  (void)hipFree(dtau);
-  (void)hipFree(dcf);
-  (void)hipFree(dx);
-  (void)hipFree(dfl);
-  (void)hipFree(dwc);
-  return rc;
+  dp.upload(e, params, (size_t)B);
+  if (q) dq.alloc<double>(e, nq);
+  if (tau) dtau.alloc<double>(e, ntau);
+  if (cf) dcf.alloc<double>(e, ncf);
+  if (x) dx.alloc<double>(e, nx);
+  if (flags) dfl.alloc<uint32_t>(e, nfl);
+  if (work_cot) dwc.alloc<double>(e, nwc);
+  if (e != hipSuccess) return hip_fail(e, "alloc/copy");
+  hs_run_args a;
+  memset(&a, 0, sizeof(a));
+  a.n_rollouts = B;
+  a.horizon = H;
+  a.k0 = k0;
+  a.n_t = n_t;
+  a.ignore_reach = ignore_reach;
+  a.params = dp.as<hs_gait_params>();
+  a.q = dq.as<double>();
+  a.tau = dtau.as<double>();
+  a.cf = dcf.as<double>();
+  a.x = dx.as<double>();
+  a.flags = dfl.as<uint32_t>();
+  a.work_cot = dwc.as<double>();
+  const int rc = hs_run(m, &a);
+  if (rc != HS_OK) return rc;
+  e = hipDeviceSynchronize();
+  dq.download(e, q, nq);
+  dtau.download(e, tau, ntau);
+  dcf.download(e, cf, ncf);
+  dx.download(e, x, nx);
+  dfl.download(e, flags, nfl);
+  dwc.download(e, work_cot, nwc);
+  return e == hipSuccess ? HS_OK : hip_fail(e, "run/copy back");
 }
 
 }  // extern "C"
 
 // ---------------------------------------------------------------------------
-// per-configuration kinematics (hs_config.hip, hs_kernels.hip)
+// per-configuration kinematics (hs_config.hip) and the pergen record (hs_kernels.hip)
 // ---------------------------------------------------------------------------
-namespace {
-
-// device scratch of a synchronous host-buffer call: freed on scope exit
-struct dev_buf {
-  void* p = nullptr;
-  hipError_t alloc(size_t bytes) { return bytes ? hipMalloc(&p, bytes) : hipSuccess; }
-  ~dev_buf() { (void)hipFree(p); }
-  template <class T>
-  T* as() const { return static_cast<T*>(p); }
-};
-
-}  // namespace
-
 extern "C" {
 
-int hs_pergen_rec(hs_model_t m, const hs_gait_params* params, int32_t B, const double* times, int32_t n_times,
-                  double* rec, void* stream) {
+// ---- the argument checks a device entry point and its host-array twin share (an empty call passes them:
+// the caller returns HS_OK before it reads an array)
+static int pergen_rec_check(hs_model_t m, const hs_gait_params* params, int32_t B, const double* times,
+                            int32_t n_times, const double* rec) {
   if (!m) return fail(HS_E_ARG, "null model");
   if (B < 0 || n_times < 0 || (int64_t)B * n_times > (int64_t(1) << 31)) return fail(HS_E_ARG, "bad batch size");
   if ((int64_t)B * n_times == 0) return HS_OK;
   if (!params || !times || !rec) return fail(HS_E_ARG, "null params, times or rec");
+  return HS_OK;
+}
+
+static int lik_check(hs_model_t m, int32_t n, const double* rec, const double* config) {
+  if (!m) return fail(HS_E_ARG, "null model");
+  if (n < 0 || n > (1 << 30)) return fail(HS_E_ARG, "bad n");
+  if (n == 0) return HS_OK;
+  if (!rec || !config) return fail(HS_E_ARG, "null rec or config");
+  return HS_OK;
+}
+
+static int fk_check(hs_model_t m, int32_t n, const double* config, int32_t stride, const double* a_ground) {
+  if (!m) return fail(HS_E_ARG, "null model");
+  if (n < 0 || n > (1 << 26)) return fail(HS_E_ARG, "bad n");
+  if (n == 0) return HS_OK;
+  if (!config || !a_ground) return fail(HS_E_ARG, "null config or a_ground");
+  if (stride < m->host.cfg) return fail(HS_E_ARG, "config_stride < config_dim");
+  return HS_OK;
+}
+
+int hs_pergen_rec(hs_model_t m, const hs_gait_params* params, int32_t B, const double* times, int32_t n_times,
+                  double* rec, void* stream) {
+  int rc = pergen_rec_check(m, params, B, times, n_times, rec);
+  if (rc != HS_OK || (int64_t)B * n_times == 0) return rc;
   const hs_topo* d = nullptr;
-  int rc = device_state(m, 0, nullptr, &d, nullptr);
+  rc = device_state(m, 0, nullptr, &d, nullptr);
   if (rc != HS_OK) return rc;
   int e = hs::launch_pergen_rec(d, params, B, times, n_times, rec, stream);
   return e ? hip_fail((hipError_t)e, "hs_pergen_rec launch") : HS_OK;
@@ -1219,33 +1226,28 @@ int hs_pergen_rec(hs_model_t m, const hs_gait_params* params, int32_t B, const d
 
 int hs_pergen_rec_host(hs_model_t m, const hs_gait_params* params, int32_t B, const double* times, int32_t n_times,
                        double* rec) {
-  if (!m) return fail(HS_E_ARG, "null model");
-  if (B < 0 || n_times < 0 || (int64_t)B * n_times > (int64_t(1) << 31)) return fail(HS_E_ARG, "bad batch size");
-  if ((int64_t)B * n_times == 0) return HS_OK;
-  if (!params || !times || !rec) return fail(HS_E_ARG, "null params, times or rec");
+  int rc = pergen_rec_check(m, params, B, times, n_times, rec);
+  if (rc != HS_OK || (int64_t)B * n_times == 0) return rc;
   const size_t len = 6 + 3 * (size_t)m->host.n_limbs, nrec = (size_t)B * n_times * len;
   dev_buf dp, dt, dr;
-  hipError_t e = dp.alloc((size_t)B * sizeof(hs_gait_params));
-  if (e == hipSuccess) e = dt.alloc((size_t)n_times * sizeof(double));
-  if (e == hipSuccess) e = dr.alloc(nrec * sizeof(double));
-  if (e == hipSuccess) e = hipMemcpy(dp.p, params, (size_t)B * sizeof(hs_gait_params), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dt.p, times, (size_t)n_times * sizeof(double), hipMemcpyHostToDevice);
+  hipError_t e = hipSuccess;
+  dp.upload(e, params, (size_t)B);
+  dt.upload(e, times, (size_t)n_times);
+  dr.alloc<double>(e, nrec);
   if (e != hipSuccess) return hip_fail(e, "alloc/copy");
-  int rc = hs_pergen_rec(m, dp.as<hs_gait_params>(), B, dt.as<double>(), n_times, dr.as<double>(), nullptr);
+  rc = hs_pergen_rec(m, dp.as<hs_gait_params>(), B, dt.as<double>(), n_times, dr.as<double>(), nullptr);
   if (rc != HS_OK) return rc;
   e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(rec, dr.p, nrec * sizeof(double), hipMemcpyDeviceToHost);
+  dr.download(e, rec, nrec);
   return e == hipSuccess ? HS_OK : hip_fail(e, "run/copy back");
 }
 
 int hs_model_lik(hs_model_t m, int32_t n, const double* rec, int32_t ignore_reach, double* config, uint32_t* status,
                  void* stream) {
-  if (!m) return fail(HS_E_ARG, "null model");
-  if (n < 0 || n > (1 << 30)) return fail(HS_E_ARG, "bad n");
-  if (n == 0) return HS_OK;
-  if (!rec || !config) return fail(HS_E_ARG, "null rec or config");
+  int rc = lik_check(m, n, rec, config);
+  if (rc != HS_OK || n == 0) return rc;
   const hs_topo* d = nullptr;
-  int rc = device_state(m, 0, nullptr, &d, nullptr);
+  rc = device_state(m, 0, nullptr, &d, nullptr);
   if (rc != HS_OK) return rc;
   int e = hs::launch_lik(d, n, rec, ignore_reach, config, status, stream);
   return e ? hip_fail((hipError_t)e, "hs_model_lik launch") : HS_OK;
@@ -1253,24 +1255,21 @@ int hs_model_lik(hs_model_t m, int32_t n, const double* rec, int32_t ignore_reac
 
 int hs_model_lik_host(hs_model_t m, int32_t n, const double* rec, int32_t ignore_reach, double* config,
                       uint32_t* status) {
-  if (!m) return fail(HS_E_ARG, "null model");
-  if (n < 0 || n > (1 << 30)) return fail(HS_E_ARG, "bad n");
-  if (n == 0) return HS_OK;
-  if (!rec || !config) return fail(HS_E_ARG, "null rec or config");
+  int rc = lik_check(m, n, rec, config);
+  if (rc != HS_OK || n == 0) return rc;
   const size_t nrec = (size_t)n * (6 + 3 * (size_t)m->host.n_limbs), ncfg = (size_t)n * m->host.cfg;
   dev_buf dr, dc, ds;
-  hipError_t e = dr.alloc(nrec * sizeof(double));
-  if (e == hipSuccess) e = dc.alloc(ncfg * sizeof(double));
-  if (e == hipSuccess) e = ds.alloc((size_t)n * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMemcpy(dr.p, rec, nrec * sizeof(double), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dc.p, config, ncfg * sizeof(double), hipMemcpyHostToDevice);  // kept entries
+  hipError_t e = hipSuccess;
+  dr.upload(e, rec, nrec);
+  dc.upload(e, config, ncfg);  // kept entries
+  ds.alloc<uint32_t>(e, (size_t)n);
   if (e != hipSuccess) return hip_fail(e, "alloc/copy");
-  int rc = hs_model_lik(m, n, dr.as<double>(), ignore_reach, dc.as<double>(), ds.as<uint32_t>(), nullptr);
+  rc = hs_model_lik(m, n, dr.as<double>(), ignore_reach, dc.as<double>(), ds.as<uint32_t>(), nullptr);
   if (rc != HS_OK) return rc;
   std::vector<uint32_t> st((size_t)n);
   e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(config, dc.p, ncfg * sizeof(double), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(st.data(), ds.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost);
+  dc.download(e, config, ncfg);
+  ds.download(e, st.data(), (size_t)n);
   if (e != hipSuccess) return hip_fail(e, "run/copy back");
   if (status) std::copy(st.begin(), st.end(), status);
   for (int32_t i = 0; i < n; i++)
@@ -1282,13 +1281,10 @@ int hs_model_lik_host(hs_model_t m, int32_t n, const double* rec, int32_t ignore
 
 int hs_model_fk(hs_model_t m, int32_t n, const double* config, int32_t stride, double* a_ground, double* a_joint,
                 void* stream) {
-  if (!m) return fail(HS_E_ARG, "null model");
-  if (n < 0 || n > (1 << 26)) return fail(HS_E_ARG, "bad n");
-  if (n == 0) return HS_OK;
-  if (!config || !a_ground) return fail(HS_E_ARG, "null config or a_ground");
-  if (stride < m->host.cfg) return fail(HS_E_ARG, "config_stride < config_dim");
+  int rc = fk_check(m, n, config, stride, a_ground);
+  if (rc != HS_OK || n == 0) return rc;
   const hs_topo* d = nullptr;
-  int rc = device_state(m, 0, nullptr, &d, nullptr);
+  rc = device_state(m, 0, nullptr, &d, nullptr);
   if (rc != HS_OK) return rc;
   int e = hs::launch_fk(d, m->host.n, n, config, stride, a_ground, a_joint, stream);
   return e ? hip_fail((hipError_t)e, "hs_model_fk launch") : HS_OK;
@@ -1296,23 +1292,20 @@ int hs_model_fk(hs_model_t m, int32_t n, const double* config, int32_t stride, d
 
 int hs_model_fk_host(hs_model_t m, int32_t n, const double* config, int32_t stride, double* a_ground,
                      double* a_joint) {
-  if (!m) return fail(HS_E_ARG, "null model");
-  if (n < 0 || n > (1 << 26)) return fail(HS_E_ARG, "bad n");
-  if (n == 0) return HS_OK;
-  if (!config || !a_ground) return fail(HS_E_ARG, "null config or a_ground");
-  if (stride < m->host.cfg) return fail(HS_E_ARG, "config_stride < config_dim");
+  int rc = fk_check(m, n, config, stride, a_ground);
+  if (rc != HS_OK || n == 0) return rc;
   const size_t ncfg = (size_t)n * stride, na = (size_t)n * m->host.n * 12;
   dev_buf dc, dg, dj;
-  hipError_t e = dc.alloc(ncfg * sizeof(double));
-  if (e == hipSuccess) e = dg.alloc(na * sizeof(double));
-  if (e == hipSuccess && a_joint) e = dj.alloc(na * sizeof(double));
-  if (e == hipSuccess) e = hipMemcpy(dc.p, config, ncfg * sizeof(double), hipMemcpyHostToDevice);
+  hipError_t e = hipSuccess;
+  dc.upload(e, config, ncfg);
+  dg.alloc<double>(e, na);
+  if (a_joint) dj.alloc<double>(e, na);
   if (e != hipSuccess) return hip_fail(e, "alloc/copy");
-  int rc = hs_model_fk(m, n, dc.as<double>(), stride, dg.as<double>(), dj.as<double>(), nullptr);
+  rc = hs_model_fk(m, n, dc.as<double>(), stride, dg.as<double>(), dj.as<double>(), nullptr);
   if (rc != HS_OK) return rc;
   e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(a_ground, dg.p, na * sizeof(double), hipMemcpyDeviceToHost);
-  if (e == hipSuccess && a_joint) e = hipMemcpy(a_joint, dj.p, na * sizeof(double), hipMemcpyDeviceToHost);
+  dg.download(e, a_ground, na);
+  dj.download(e, a_joint, na);
   return e == hipSuccess ? HS_OK : hip_fail(e, "run/copy back");
 }
 

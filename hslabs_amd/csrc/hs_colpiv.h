@@ -1,5 +1,5 @@
 // hs_colpiv.h -- Eigen 3.3's ColPivHouseholderQR for one wavefront, sized at run time, everything in LDS:
-// the column-norm downdate, the nonzero-pivot rule and the solve as hs_kernels.hip's colpiv_qr / qr_solve
+// the column-norm downdate, the nonzero-pivot rule and the solve as hs_step_solve.h's colpiv_qr / qr_solve
 // restate them for the square systems of the contact solve. Used by the regression of accelerations on
 // torques (hs_sim_probe.hip: rectangular, m x (nmj + 1)) and by the configuration path controller
 // (hs_cpc.hip: the two square nmj x nmj systems of compute_b and B_chi_dec).

@@ -65,7 +65,7 @@ struct launch_map {
   int32_t st_tau, st_cf, st_q, st_x;  // output row strides (mixed: maxima over the models)
   // fused steps (hs_run_calls): one launch runs fused_n steps x fused_w wavefronts, wavefront
   // blockIdx -> (local step, batch wavefront) by groups of batch wavefronts (fused_coords in
-  // hs_kernels.hip: a group's steps in order, its wavefronts fastest); global step s = fused_s0 + local step is
+  // hs_step_base.h: a group's steps in order, its wavefronts fastest); global step s = fused_s0 + local step is
   // call s / fused_h, step s % fused_h of that call, output row s; the step's work goes to
   // fused_work[s][b] (summed in order afterwards), the general-path scratch to
   // fused_gen[local step][b]. setup_only: store the gait setup and return.
@@ -121,8 +121,8 @@ void ktab_range(int32_t k0, int32_t n_t, int32_t horizon, int64_t n_calls, int32
                 int32_t* n_ttab);
 launch_map single_model_map(const hs_topo& t, int32_t n_rollouts);
 
-// The kernel launchers of one precision's build of hs_kernels.hip (hs_kernels_f32.hip is the single
-// precision build of the same kernels: outputs are float). They return hipError_t values.
+// The kernel launchers of one precision's unit of the step kernels (hs_kernels.hip: fp64; hs_kernels_f32.hip:
+// the same headers in single precision, outputs are float; launchers in hs_rollout_kernel.h and hs_limb.h). They return hipError_t values.
 struct kernels {
   // `workspace` holds general_workspace_bytes() per rollout + 1 (global-memory scratch of the
   // conditioning fallback; the extra slot serves idle half-waves)

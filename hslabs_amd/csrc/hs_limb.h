@@ -1,5 +1,7 @@
-// hs_limb.h -- the limb-lane step kernel (round 6), included by hs_kernels.hip inside its anonymous
-// namespace (both precisions).
+// hs_limb.h -- the limb-lane step kernel (round 6) and its launcher, the default kernel of hs_run_calls. Built
+// on the step's shared parts (hs_step_base.h, hs_step_kin.h, hs_step_solve.h) and the tile planner
+// (hs_limb_tile.h); it needs nothing of hs_rollout_kernel.h. Included by both units (hs_kernels.hip,
+// hs_kernels_f32.hip), each with its own copy in its anonymous namespace.
 //
 // hs_rollout_kernel maps a rollout to 32 lanes and each phase to the lanes it can use: kinematics 30
 // (sample, limb) lanes, dynamics and the particular solution one lane per part, the contact blocks four
@@ -28,12 +30,14 @@
 // groups through LDS (limb_tile_kd); routed by limb_tile() in hs_capi.cpp, the same outputs bitwise
 // (tests/test_gpu_limb_tile.py). In step mode a tile-mapped wavefront runs several tiles of its rollout in turn
 // (the tile loop, launch_map::limb_tile_loop; tests/test_gpu_limb_tile_loop.py).
+#pragma once
+#include "hs_limb_tile.h"
+#include "hs_step_base.h"
+#include "hs_step_kin.h"
+#include "hs_step_solve.h"
 
-#ifndef HS_LIMB_GROUP
-// the fused launch's block order for the limb kernel (fused_coords): groups of this many batch wavefronts
-// (8 rollouts each), each group's steps in order
-#define HS_LIMB_GROUP HS_FUSED_GROUP
-#endif
+namespace {
+
 #ifndef HS_LIMB_WAVES
 #define HS_LIMB_WAVES 2  // waves per SIMD the limb kernel is built for
 #endif
@@ -1458,8 +1462,7 @@ __global__ __launch_bounds__(WAVE, HS_REAL_IS_FLOAT ? HS_LIMB_WAVES_F32 : HS_LIM
   int fstep = 0, q = (int)blockIdx.x;
   // tile mapping: the block's virtual step is (chunk of tiles, rollout of the batch wavefront's eight)
   const int nt = TILE ? limb_tile_count(mp.fused_n) : 0, tl = LOOP ? mp.limb_tile_loop : 1;
-  fused_coords<HS_LIMB_GROUP>((int)blockIdx.x, mp.fused_w, TILE ? HS_TILE_SLOTS * limb_tile_chunks(nt, tl) : mp.fused_n, fstep,
-                              q);
+  fused_coords((int)blockIdx.x, mp.fused_w, TILE ? HS_TILE_SLOTS * limb_tile_chunks(nt, tl) : mp.fused_n, fstep, q);
   const hs_topo* __restrict__ T = mp.limb_model ? T0 + mp.limb_model[q] : T0;  // a mixed plan's wavefront model
   STAMP(18);
   {  // the link records, 8 bytes per lane and load
@@ -1549,3 +1552,53 @@ __global__ __launch_bounds__(WAVE, HS_REAL_IS_FLOAT ? HS_LIMB_WAVES_F32 : HS_LIM
     limb_step<NM, FORCES, TILE, false>(sh, T, a, mp, h, TILE ? fstep / LGR : fstep, true, plan...);
   }
 }
+
+}  // namespace
+
+namespace hs {
+
+static int limb_deferred(unsigned long long* out) {
+  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_limb_deferred), sizeof(unsigned long long), 0,
+                                  hipMemcpyDeviceToHost);
+}
+
+static int launch_limb(const hs_topo* d_topo, const hs_run_args& a, void* workspace, const launch_map& mp,
+                       int32_t tile_plan, int32_t* tile_planned) {
+  if (tile_planned) *tile_planned = 0;
+  if (a.n_rollouts <= 0 || mp.fused_n <= 0) return 0;
+  hipStream_t st = (hipStream_t)a.stream;
+  RolloutWS* ws = (RolloutWS*)workspace;
+  launch_map m = mp;
+  m.fused_w = mp.limb_rollouts ? mp.limb_waves : (a.n_rollouts + LGR - 1) / LGR;  // wavefronts per step: 8 rollouts each
+  // the tile loop: a wavefront per chunk of limb_tile_loop tiles
+  // (forces mode and the fp32 build: a tile per wavefront, their instantiations have no tile loop)
+  m.limb_tile_loop = mp.limb_tile_loop < 1 || mp.tau_in || HS_REAL_IS_FLOAT ? 1 : mp.limb_tile_loop;
+  const int wsteps = mp.limb_tile ? HS_TILE_SLOTS * limb_tile_chunks(limb_tile_count(mp.fused_n), m.limb_tile_loop) : mp.fused_n;
+  const dim3 grid((unsigned)((int64_t)m.fused_w * wsteps));
+  // the tile mapping's slot sequence as the kernel's tile descriptor (hs_limb_tile.h: limb_tile_desc_build, which
+  // reads tile_plan). (A launch no descriptor holds is routed to the packed mapping by limb_tile() in hs_capi.cpp.)
+  limb_tile_desc plan = {};
+  if (mp.limb_tile) {
+    const limb_tile_launch L = {mp.fused_n, mp.fused_s0, mp.fused_h, a.k0, a.n_t, mp.ktab_nl > 0 ? mp.ktab_nl : HS_LMAX};
+    bool planned = false;
+    if (!limb_tile_desc_build(L, tile_plan, plan, &planned)) return (int)hipErrorInvalidValue;
+    if (tile_planned) *tile_planned = planned;
+  }
+  with_lds_class(mp.max_parts, [&](auto nm) {
+    constexpr int NM = decltype(nm)::value;
+    if (mp.tau_in) {  // solve_forces (hs_run_forces_calls)
+      if (mp.limb_tile)
+        hipLaunchKernelGGL((hs_limb_kernel<NM, true, true, limb_tile_desc>), grid, dim3(WAVE), 0, st, d_topo, a, ws, m, plan);
+      else
+        hipLaunchKernelGGL((hs_limb_kernel<NM, true, false>), grid, dim3(WAVE), 0, st, d_topo, a, ws, m);
+    } else {
+      if (mp.limb_tile)
+        hipLaunchKernelGGL((hs_limb_kernel<NM, false, true, limb_tile_desc>), grid, dim3(WAVE), 0, st, d_topo, a, ws, m, plan);
+      else
+        hipLaunchKernelGGL((hs_limb_kernel<NM, false, false>), grid, dim3(WAVE), 0, st, d_topo, a, ws, m);
+    }
+  });
+  return (int)hipGetLastError();
+}
+
+}  // namespace hs

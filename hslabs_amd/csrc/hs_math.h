@@ -6,7 +6,8 @@
 // bottom row. Its rounding follows the compiling file's contraction flag
 // (hslabs_amd/build.py): hs_config.hip and hs_sim.hip (-ffp-contract=off) round
 // like the reference's x86-64 -O2 build; the rollout kernels (fast) fuse a*b+c.
-// `real` is double, or float for the fp32 build (hs_kernels_f32.hip).
+// `real` is double, or float for the step kernels' fp32 unit (hs_kernels_f32.hip sets HS_REAL and
+// HS_REAL_IS_FLOAT before its first include).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -17,7 +18,7 @@
 #endif
 
 namespace hsd {
-// one instantiation per precision (hs_kernels.hip: double, hs_kernels_f32.hip: float)
+// one instantiation per precision (the units hs_kernels.hip: double, hs_kernels_f32.hip: float)
 #if HS_REAL_IS_FLOAT
 inline namespace f32 {
 #else

@@ -1644,7 +1644,7 @@ bool aug_solve(int nc, const std::vector<double>& A, const std::vector<double>& 
 // e_c = d0_c - mean d0 (c2(C) / tr(C) is G's smallest eigenvalue mu2 + mu3 within 4x); the ratio
 // follows the reference's 6th FullPivLU pivot ratio within ~2x, and every retry measured in tree mode
 // had it below 2.5e-5 (tests/test_oracle.py::test_zeroth_guard_*). The kernel's division-free form
-// (zeroth_well_posed in hs_kernels.hip): C' = nc Q - s s^T (s = sum d0_c, Q = sum d0_c d0_c^T),
+// (zeroth_well_posed in hs_step_solve.h): C' = nc Q - s s^T (s = sum d0_c, Q = sum d0_c d0_c^T),
 // c2(C') >= 1e-3 * nc * tr(C') * maxdiag(G).
 constexpr double kZerothGuard = 1e-3;
 bool zeroth_well_posed(const DynRec& d, const std::vector<int>& cf) {
@@ -1751,7 +1751,7 @@ bool fast_contact_solve(const hso_model* m, const DynRec& d, const std::vector<d
   if (!zeroth_well_posed(d, cf)) return false;
   // Schur complement on the 6 zeroth-order constraints
   // per-contact blocks, summed over the contacts pairwise as the kernel's lanes do
-  // (((c3 + c2) + (c1 + c0)) + ((c7 + c6) + (c5 + c4)), absent contacts 0: hs_kernels.hip fast_solve_lanes)
+  // (((c3 + c2) + (c1 + c0)) + ((c7 + c6) + (c5 + c4)), absent contacts 0: hs_step_solve.h fast_solve_lanes)
   double Sc[8][36] = {}, hc[8][6] = {};
   std::vector<double> Dinv(9 * nc);
   for (int c = 0; c < nc; c++) {

@@ -1,7 +1,7 @@
 """Algorithmic FP64 FLOPs per control-loop step, counted by the
 oracle compiled with a counting double (oracle/hs_oracle_flops.cpp, flopcount.h) on the kernel's
 own path: BASIS_FAST = the tree-built null basis + the closed-form contact solve (the Eigen-style
-rank loop where the closed form declines), same operation sequence as hs_kernels.hip.
+rank loop where the closed form declines), same operation sequence as the step kernels (hs_step_kin.h, hs_step_solve.h).
 
 Two figures per workload, on a sample of the bench's synthetic gaits (hslabs_amd/synth.py):
   algorithmic  one cycle per rollout (k0 = 0, H = n_t): every trajectory sample's kinematics once,

@@ -107,7 +107,7 @@ def check(lib: str, verbose: bool = True) -> int:
 
 _MUL_F64 = re.compile(r"^v_mul_f64(?:_e(?:32|64))?\s+(v\[\d+:\d+\])")
 _ADD_F64 = re.compile(r"^v_add_f64(?:_e(?:32|64))?\s+v\[\d+:\d+\],\s*(\S+),\s*(\S+)")
-WORK_ADD_UNROLL = 32  # reduce_rollouts' unrolled step loop (hs_kernels.hip)
+WORK_ADD_UNROLL = 32  # reduce_rollouts' unrolled step loop (hs_step_solve.h)
 
 
 def mul_add_pairs(instructions) -> int:

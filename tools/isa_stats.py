@@ -1,5 +1,6 @@
-"""Per-function register / scratch / LDS / code-size summary of the device code of
-hs_kernels.hip (hipcc -S for gfx950). Tuning aid only.
+"""Per-function register / scratch / LDS / code-size summary of the device code of a unit of the step
+kernels (hipcc -S for gfx950; default hs_kernels.hip, the fp64 unit; --src .../hs_kernels_f32.hip: the fp32
+one). Tuning aid only.
 
   python tools/isa_stats.py [-D NAME=VAL ...] [--src file.hip] [--filter substr]
 """

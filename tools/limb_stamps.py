@@ -1,5 +1,5 @@
-"""Per-phase shader-clock breakdown of the limb-lane step kernel (hs_limb.h; diagnostic -DHS_STAMPS build
-libhslabs_stamps.so, tools/stamps.py's). Runs the bench's fused path (hexapod B = 4096, 20 calls) and prints
+"""Per-phase shader-clock breakdown of the limb-lane step kernel (hs_limb.h; the stamp
+table is hs_step_base.h's, its readers hs_kernels.hip's; diagnostic -DHS_STAMPS build libhslabs_stamps.so, tools/stamps.py's). Runs the bench's fused path (hexapod B = 4096, 20 calls) and prints
 mean / p50 / p90 cycles per phase over the wavefronts of one window of the launch (STEP=s: blocks from
 s * 512). Tuning aid only.   python tools/limb_stamps.py [--build] [--steps K] [--tile]
 --steps K: K calls instead of 20. --tile: the tile mapping at any K (HS_LIMB_TILE_MIN=1), its phases named

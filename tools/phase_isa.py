@@ -1,6 +1,6 @@
-"""Static instruction mix per stamped phase of hs_rollout_kernel (diagnostic; tuning aid only).
+"""Static instruction mix per stamped phase of hs_rollout_kernel (hs_rollout_kernel.h; diagnostic; tuning aid only).
 
-Compiles the HS_STAMPS build to assembly, slices the chosen kernel at its
+Compiles the HS_STAMPS build of the fp64 unit (hs_kernels.hip) to assembly, slices the chosen kernel at its
 s_memtime stamps (slot = the store offset / 8) and counts instruction classes
 between consecutive stamps in code order.
 

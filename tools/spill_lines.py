@@ -1,6 +1,6 @@
-"""Source lines of the scratch (spill) accesses of one kernel of hs_kernels.hip (tuning aid): compiles
-the device code with line tables (-gline-tables-only) and attributes each scratch_* instruction of the
-kernel to the .loc line before it.
+"""Source lines of the scratch (spill) accesses of one step kernel (tuning aid): compiles the device code
+of a unit (hs_kernels.hip, hs_kernels_f32.hip) with line tables (-gline-tables-only) and attributes each
+scratch_* instruction of the kernel to the .loc line before it, as header:line (hs_step_solve.h:..., hs_limb.h:...).
 
   python tools/spill_lines.py [-D NAME=VAL ...] [--kernel substr]   (default: the fused hexapod step launch)
 """
@@ -20,7 +20,7 @@ def main():
     ap.add_argument("-D", action="append", default=[])
     ap.add_argument("--kernel", default="hs_rollout_kernelILi22ELb0ELi1E")
     ap.add_argument("--src", default=SRC, help="the csrc directory (e.g. an older commit's, tools/build_prev.py)")
-    ap.add_argument("--file", default="hs_kernels.hip", help="hs_kernels_f32.hip: the fp32 build")
+    ap.add_argument("--file", default="hs_kernels.hip", help="the unit (hs_kernels_f32.hip: the fp32 one)")
     args = ap.parse_args()
     with tempfile.TemporaryDirectory() as td:
         out = os.path.join(td, "k.s")
