@@ -158,6 +158,9 @@ int hso_sim_run(const hso_model* m, const double* p10, int iterations, int n_t, 
                 const double* dq_tab, const double* tau_tab, double* body, uint32_t* seed, int32_t* tsi,
                 int n_steps, double* tau_cmd, double* q_meas, double* torso, int32_t* n_contacts,
                 double* normal_force);
+/* The signed penetration d the plane collision tests for every part of a body state (d >= 0: a
+ * contact of the step taken from it): depth [n], NaN for a part without a capsule or sphere. */
+int hso_sim_contact_depths(const hso_model* m, const double* body, double* depth);
 
 #ifdef __cplusplus
 }

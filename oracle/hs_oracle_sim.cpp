@@ -442,31 +442,37 @@ void contact_info2(const SimJoint& J, const std::vector<SimBody>& B, const SimPa
 }
 
 // dCollideCapsulePlane / dCollideSpherePlane against the plane (0,0,1,0); 1 contact
-bool collide_plane(const Node& nd, const SimBody& b, double* cpos, double* depth) {
-  const double n[3] = {0, 0, 1};
+// plane_depth: the signed penetration d both tests decide on, and the point p (the capsule's lower cap
+// centre, the sphere's centre) the contact position hangs from; NaN for a part with neither geom
+double plane_depth(const Node& nd, const SimBody& b, const double* n, double* p) {
   if (nd.gtype == 2) {
     double sign = (dot3_14(n, b.R + 2) > 0) ? -1.0 : 1.0;
-    double p[3];
     p[0] = b.pos[0] + b.R[2] * nd.glen * 0.5 * sign;
     p[1] = b.pos[1] + b.R[6] * nd.glen * 0.5 * sign;
     p[2] = b.pos[2] + b.R[10] * nd.glen * 0.5 * sign;
     double k = dot3(p, n);
-    double d = 0 - k + nd.gr;
-    if (d < 0) return false;
-    for (int i = 0; i < 3; i++) cpos[i] = p[i] - n[i] * nd.gr;
-    *depth = d;
-    return true;
+    return 0 - k + nd.gr;
   }
   if (nd.gtype == 1) {
+    for (int i = 0; i < 3; i++) p[i] = b.pos[i];
     double k = dot3(b.pos, n);
-    double d = 0 - k + nd.gr;
-    if (d >= 0) {
-      for (int i = 0; i < 3; i++) cpos[i] = b.pos[i] - n[i] * nd.gr;
-      *depth = d;
-      return true;
-    }
+    return 0 - k + nd.gr;
   }
-  return false;
+  return NAN;
+}
+
+bool collide_plane(const Node& nd, const SimBody& b, double* cpos, double* depth) {
+  const double n[3] = {0, 0, 1};
+  double p[3];
+  double d = plane_depth(nd, b, n, p);
+  if (nd.gtype == 2) {
+    if (d < 0) return false;
+  } else if (!(nd.gtype == 1 && d >= 0)) {
+    return false;
+  }
+  for (int i = 0; i < 3; i++) cpos[i] = p[i] - n[i] * nd.gr;
+  *depth = d;
+  return true;
 }
 
 struct StepOut {
@@ -704,6 +710,17 @@ int hso_sim_hinges(const hso_model* m, const double* body, double* q, double* dq
     const SimJoint& J = T.joints[T.motors[j]];
     if (q) q[j] = hinge_angle(J, B);
     if (dq) dq[j] = hinge_rate(J, B);
+  }
+  return 0;
+}
+
+int hso_sim_contact_depths(const hso_model* m, const double* body, double* depth) {
+  std::vector<SimBody> B;
+  load_bodies(m->n, body, B);
+  const double n[3] = {0, 0, 1};
+  for (int p = 0; p < m->n; p++) {
+    double pt[3];
+    depth[p] = plane_depth(m->nodes[p], B[p], n, pt);
   }
   return 0;
 }

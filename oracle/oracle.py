@@ -137,7 +137,10 @@ def build() -> str:
     return LIB_PATH
 
 
+F32_LIB_PATH = os.path.join(HERE, "_build", "libhs_oracle_f32.so")
+
 _lib = None
+_lib_f32 = None
 _perf = {}
 
 
@@ -148,6 +151,18 @@ def lib():
             build()
         _lib = _bind(LIB_PATH)
     return _lib
+
+
+def lib_f32():
+    """The single-precision build (hs_oracle_f32.cpp: every double an f32r of f32round.h, rounded through
+    float after every operation): Model(path, L=lib_f32()) owns a model of it, and the sim_* helpers and
+    controller_tables then run in float. Same exports and double arrays as lib()."""
+    global _lib_f32
+    if _lib_f32 is None:
+        if not os.path.exists(F32_LIB_PATH):
+            build()
+        _lib_f32 = _bind(F32_LIB_PATH)
+    return _lib_f32
 
 
 def perf_lib(tag: str, timeout: float = 180.0):
@@ -206,11 +221,36 @@ def _bind(path):
                               ctypes.c_int, dp, dp, dp, ip, dp]
     L.hso_sim_batch.argtypes = [ctypes.c_void_p, dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, dp, dp, dp, dp,
                                 up, ip, ctypes.c_int, ctypes.c_int]
+    L.hso_sim_contact_depths.argtypes = [ctypes.c_void_p, dp, dp]
     return L
 
 
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+
+
+def _in(model, a):
+    """a C-contiguous float64 copy of an input array for the build that owns the model: the
+    single-precision build is handed float values (rounded here, so that its comparisons and copies
+    see what its arithmetic would)"""
+    a = np.array(a, dtype=np.float64, order="C")
+    if model.L is _lib_f32:
+        with np.errstate(over="ignore", under="ignore"):
+            a = a.astype(np.float32).astype(np.float64)
+    return a
+
+
+def _gait_in(model, gait):
+    """the C record of a gait for the build that owns the model (float values for the single-precision one)"""
+    g = gait.to_c()
+    if model.L is _lib_f32:
+        for name, ctype in Gait._fields_:
+            if ctype is ctypes.c_double:
+                setattr(g, name, float(np.float32(getattr(g, name))))
+            elif ctype is not ctypes.c_int32:
+                for i in range(3):
+                    getattr(g, name)[i] = float(np.float32(getattr(g, name)[i]))
+    return g
 
 
 @dataclass
@@ -264,10 +304,10 @@ def rollout(model: Model, gait: GaitParams, n_t: int = 20, k0: int = 0, H: int |
     flags = np.zeros(H, dtype=np.uint32)
     wc = np.zeros(2)
     diag = np.zeros((H, 4))
-    g = gait.to_c()
-    rc = lib().hso_rollout(model.handle, ctypes.byref(g), n_t, k0, H, basis, int(ignore_reach),
-                           _ptr(q), _ptr(tau), _ptr(cf), _ptr(x),
-                           flags.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), _ptr(wc), _ptr(diag))
+    g = _gait_in(model, gait)
+    rc = model.L.hso_rollout(model.handle, ctypes.byref(g), n_t, k0, H, basis, int(ignore_reach),
+                             _ptr(q), _ptr(tau), _ptr(cf), _ptr(x),
+                               flags.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), _ptr(wc), _ptr(diag))
     if rc != 0:
         raise RuntimeError(f"oracle rollout failed rc={rc}")
     return dict(q=q, tau=tau, cf=cf, x=x, flags=flags, work=wc[0], cot=wc[1], diag=diag)
@@ -462,18 +502,27 @@ class SimParams:
 
 def sim_reset(model: Model, config) -> np.ndarray:
     """init_play_config (player.cpp:351-356): body states [n][13] of a configuration."""
-    c = np.ascontiguousarray(config, dtype=np.float64)
+    c = _in(model, config)
     body = np.zeros((model.n, SIM_BODY))
-    lib().hso_sim_reset(model.handle, _ptr(c), _ptr(body))
+    model.L.hso_sim_reset(model.handle, _ptr(c), _ptr(body))
     return body
 
 
 def sim_hinges(model: Model, body):
-    b = np.ascontiguousarray(body, dtype=np.float64)
+    b = _in(model, body)
     q = np.zeros(model.nmj)
     dq = np.zeros(model.nmj)
-    lib().hso_sim_hinges(model.handle, _ptr(b), _ptr(q), _ptr(dq))
+    model.L.hso_sim_hinges(model.handle, _ptr(b), _ptr(q), _ptr(dq))
     return q, dq
+
+
+def sim_contact_depths(model: Model, body) -> np.ndarray:
+    """The signed penetration d of every part [n] that the plane collision of a step from `body` tests
+    (d >= 0: that part is a contact of the step); NaN for a part without a capsule or sphere."""
+    b = _in(model, body)
+    d = np.zeros(model.n)
+    model.L.hso_sim_contact_depths(model.handle, _ptr(b), _ptr(d))
+    return d
 
 
 def controller_tables(model: Model, gait: GaitParams, n_t: int, ignore_reach: bool = True):
@@ -484,27 +533,24 @@ def controller_tables(model: Model, gait: GaitParams, n_t: int, ignore_reach: bo
     d = q[3:n_t + 3] - q[1:n_t + 1]
     d = np.where(d > np.pi, d - 2 * np.pi, np.where(d < -np.pi, d + 2 * np.pi, d))
     dt = gait.period / n_t
-    return q[2:n_t + 2].copy(), d / (2 * dt), r["tau"].copy()
+    return _in(model, q[2:n_t + 2]), _in(model, d / (2 * dt)), _in(model, r["tau"])  # the rates: NumPy's, rounded
 
 
 def sim_run(model: Model, params: SimParams, n_t: int, q_tab, dq_tab, tau_tab, body, seed: int, tsi: int,
             n_steps: int) -> dict:
     """n_steps of modelplayer::simulate_ode for one rollout. Returns the new state and per-step outputs."""
-    body = np.array(body, dtype=np.float64, copy=True)
-    q_tab = np.ascontiguousarray(q_tab, dtype=np.float64)
-    dq_tab = np.ascontiguousarray(dq_tab, dtype=np.float64)
-    tau_tab = np.ascontiguousarray(tau_tab, dtype=np.float64)
+    body, q_tab, dq_tab, tau_tab = (_in(model, a) for a in (body, q_tab, dq_tab, tau_tab))
     sd = np.array([seed], dtype=np.uint32)
     ts = np.array([tsi], dtype=np.int32)
     out = dict(tau_cmd=np.zeros((n_steps, model.nmj)), q_meas=np.zeros((n_steps, model.nmj)),
                torso=np.zeros((n_steps, 3)), n_contacts=np.zeros(n_steps, np.int32),
                normal_force=np.zeros(n_steps))
-    p10 = params.p10()
+    p10 = _in(model, params.p10())
     ip = ctypes.POINTER(ctypes.c_int32)
-    rc = lib().hso_sim_run(model.handle, _ptr(p10), params.iterations, n_t, _ptr(q_tab), _ptr(dq_tab),
-                           _ptr(tau_tab), _ptr(body), sd.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
-                           ts.ctypes.data_as(ip), n_steps, _ptr(out["tau_cmd"]), _ptr(out["q_meas"]),
-                           _ptr(out["torso"]), out["n_contacts"].ctypes.data_as(ip), _ptr(out["normal_force"]))
+    rc = model.L.hso_sim_run(model.handle, _ptr(p10), params.iterations, n_t, _ptr(q_tab), _ptr(dq_tab),
+                             _ptr(tau_tab), _ptr(body), sd.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                             ts.ctypes.data_as(ip), n_steps, _ptr(out["tau_cmd"]), _ptr(out["q_meas"]),
+                             _ptr(out["torso"]), out["n_contacts"].ctypes.data_as(ip), _ptr(out["normal_force"]))
     if rc != 0:
         raise RuntimeError(f"oracle sim_run failed rc={rc}")
     out.update(body=body, seed=int(sd[0]), tsi=int(ts[0]))

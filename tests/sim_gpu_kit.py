@@ -1,7 +1,8 @@
 """What the closed-loop simulation's GPU test files share (test_gpu_sim*.py, test_gpu_cpc.py): the fixtures,
 the model dictionaries, the batch makers, the readers of a batch's tables and outputs, the moved batches of
-the dynamics and CPC tests, and the body bound every one of them holds. Not a test module: the test files
-import from it by name (the fixtures included)."""
+the dynamics and CPC tests, the body bound every fp64 one of them holds, and the fp32 kernels' bound against the
+two builds of the oracle (hold_to_oracles). Not a test module: the test files import from it by name (the
+fixtures included)."""
 import os
 
 import numpy as np
@@ -95,6 +96,78 @@ def moved(gpu, models, name, dtype=None):
 def moved64(gpu, models):
     """name -> (batch, tau0, history); read only: tests copy what they advance"""
     return {name: moved(gpu, models, name) for name in CASES}
+
+
+# ---- the fp32 kernels against the two builds of the oracle (test_gpu_sim_f32_oracle.py)
+def tables0(sb):
+    """rollout 0's controller tables as float64 (a batch of one pgs setup holds the same tables B times)"""
+    return [t[0].cpu().numpy().astype(np.float64) for t in (sb.tables.q, sb.tables.dq, sb.tables.tau)]
+
+
+def set_states(sb, states):
+    """Rollout k of the float batch sb becomes teacher state k (tests/test_sim_oracle_f32.py::teacher_states:
+    float-valued bodies, that step's seed and tsi); rollouts past the last state become copies of state 0."""
+    import torch
+
+    bodies, seeds, tsis = states[:3]
+    assert sb.dtype == torch.float32 and sb.B >= len(bodies)
+    assert np.array_equal(bodies, bodies.astype(np.float32).astype(np.float64))
+    pad = sb.B - len(bodies)
+    ext = lambda a: np.concatenate([a, np.repeat(a[:1], pad, axis=0)]) if pad else a  # noqa: E731
+    sb.body.copy_(torch.as_tensor(ext(bodies).astype(np.float32), device=sb.device))
+    sb.seed.copy_(torch.as_tensor(ext(seeds).astype(np.uint32).view(np.int32), device=sb.device))
+    sb.tsi.copy_(torch.as_tensor(ext(tsis).astype(np.int32), device=sb.device))
+    torch.cuda.synchronize()
+
+
+def one_step_results(sb, o, K=None):
+    """what tests/test_sim_oracle_f32.py::single_steps returns, of the first K rollouts of a batch after a
+    one-step launch with the outputs o (float64 / uint32 on the host)"""
+    K = sb.B if K is None else K
+    res = {k: v[:K, 0].cpu().numpy().astype(np.float64) for k, v in o.items() if k not in ("n_contacts", "state", "fall_z")}
+    res["n_contacts"] = o["n_contacts"][:K, 0].cpu().numpy()
+    res["body"] = sb.body[:K].cpu().numpy().astype(np.float64)
+    res["seed"] = sb.seed[:K].cpu().numpy().view(np.uint32)
+    res["tsi"] = sb.tsi[:K].cpu().numpy()
+    return res
+
+
+def hold_to_oracles(what, kern, r64, r32, near, quantities, factor=4.0, cap=True):
+    """The bound of the fp32 kernels. near [K]: per state, the parts with |d| <= MARGIN (0: decided).
+    On decided states: n_contacts and the seed are the fp64 oracle's, and for every quantity
+    |kernel - f64 oracle| <= factor * spread, spread = the largest |f32 oracle - f64 oracle| over the decided
+    states, all relative to max(1, |f64 value|). On undecided states: the contact count is within `near` of the
+    oracle's, and where it agrees the seed and the quantities are held as on decided ones. cap: the share of
+    undecided states is asserted (UNDECIDED_CAP). Returns quantity -> (spread, kernel vs f64, kernel vs f32)."""
+    from test_sim_oracle_f32 import assert_decided_steps_agree, deviation
+
+    if cap:
+        decided = assert_decided_steps_agree(r32, r64, near)
+    else:
+        decided = near == 0
+        assert decided.any()
+        assert np.array_equal(r32["n_contacts"][decided], r64["n_contacts"][decided])
+        assert np.array_equal(r32["seed"][decided], r64["seed"][decided])
+    assert np.array_equal(kern["n_contacts"][decided], r64["n_contacts"][decided]), what
+    assert np.array_equal(kern["seed"][decided], r64["seed"][decided]), what
+    off = np.abs(kern["n_contacts"].astype(np.int64) - r64["n_contacts"])
+    assert (off <= near).all(), (what, off[~decided], near[~decided])
+    same = off == 0
+    assert np.array_equal(kern["seed"][same], r64["seed"][same]), what  # the same rows, the same draws
+    res, fails = {}, []
+    for q in quantities:
+        spread = float(deviation(r32[q], r64[q])[decided].max())
+        k64, k32 = deviation(kern[q], r64[q]), deviation(kern[q], r32[q])
+        res[q] = (spread, float(k64[decided].max()), float(k32[decided].max()))
+        times = lambda v: f"{v / spread:.2f} x" if spread > 0 else ("equal" if v == 0 else "inf x")  # noqa: E731
+        print(f"{what} {q}: spread {spread:.2e}, kernel vs f64 {res[q][1]:.2e} ({times(res[q][1])}), "
+              f"kernel vs f32 oracle {res[q][2]:.2e} ({times(res[q][2])}); undecided with equal counts "
+              f"{int((same & ~decided).sum())} of {int((~decided).sum())}: "
+              f"{float(k64[same & ~decided].max()) if (same & ~decided).any() else 0.0:.2e}")
+        if not k64[same].max() <= factor * spread:
+            fails.append((q, float(k64[same].max()), factor * spread))
+    assert not fails, (what, fails)
+    return res
 
 
 def copy_state(dst, src):

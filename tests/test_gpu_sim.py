@@ -168,7 +168,8 @@ def test_every_part_in_contact(gpu, hmodels, oracle_mod, omodels, name):
 # ---- single precision (HS_PREC_F32, BASELINE configs[2] "fp32"): same algorithm in float.
 # Floats cannot follow the double trajectories bit for bit, so these check the reset against
 # the oracle to float rounding, closed-form physics, the fp32 path's own determinism, and that
-# its trajectories stay near the fp64 ones over configs[2]'s 32-step horizon.
+# its trajectories stay near the fp64 ones over configs[2]'s 32-step horizon. The tight bound is per step:
+# tests/test_gpu_sim_f32_oracle.py holds single teacher-forced steps to the oracle's single-precision build.
 
 @pytest.mark.parametrize("name", ["hexapod", "spider", "myant"])
 def test_f32_reset_matches_oracle(gpu, hmodels, oracle_mod, omodels, name):

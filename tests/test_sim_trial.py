@@ -36,15 +36,18 @@ MARGIN = 1e-6
 
 
 def oracle_trial(O, om, n_t, qt, dqt, tt, body0, tsi0, n_steps, dv=None, kick_every=0, kick_phase=0, hc=0.0,
-                 check_from=0, check_until=-1, limit=0.0, open_loop=False):
+                 check_from=0, check_until=-1, limit=0.0, open_loop=False, seed0=0, k_open=1e-300, real=np.float64):
     """One rollout of the trial semantics on the oracle. Returns state, the fall height, the final
     body / seed / tsi, `heights` (root z seen before every step reached, the freezing check's last)
-    and the per-step outputs of the steps taken."""
-    body, seed, tsi = np.array(body0, dtype=np.float64), 0, int(tsi0)
+    and the per-step outputs of the steps taken. seed0: the dRand state it starts with. For a model of
+    the single-precision build (oracle.lib_f32()): k_open, the k of the open-loop steps, one that float
+    holds (tests/test_sim_oracle_f32.py K_OPEN_F32), and real = np.float32, the type the emulated PD torque
+    and its clip are formed in."""
+    body, seed, tsi = np.array(body0, dtype=np.float64), int(seed0), int(tsi0)
     nmj = tt.shape[1]
     P = O.SimParams()
-    Pff = O.SimParams(k=1e-300)
-    k1, k2 = -P.k, -2 * np.sqrt(P.k)
+    Pff = O.SimParams(k=k_open)
+    k1, k2 = real(-P.k), real(-2) * np.sqrt(real(P.k))
     out = dict(tau_cmd=[], q_meas=[], torso=[], n_contacts=[], normal_force=[])
     heights, state, fall_z = [], RUNNING, np.nan
     for _ in range(n_steps):
@@ -64,14 +67,14 @@ def oracle_trial(O, om, n_t, qt, dqt, tt, body0, tsi0, n_steps, dv=None, kick_ev
         if open_loop:
             r = O.sim_run(om, Pff, n_t, qt, dqt, tt, b, seed, tsi, 1)
         elif limit > 0:
-            qm, dqm = O.sim_hinges(om, b)
-            a1 = qm - qt[hrow, 6:]
-            a2 = dqm - dqt[hrow, 6:]
+            qm, dqm = (v.astype(real) for v in O.sim_hinges(om, b))
+            a1 = qm - qt[hrow, 6:].astype(real)
+            a2 = dqm - dqt[hrow, 6:].astype(real)
             a1 = np.where(a1 > np.pi, a1 - 2 * np.pi, np.where(a1 <= -np.pi, a1 + 2 * np.pi, a1))
             a1 = a1 * k1
             a2 = a2 * k2
             a1 = a1 + a2
-            tau = tt[hrow] + a1
+            tau = tt[hrow].astype(real) + a1
             big = np.abs(tau) > limit
             tau = np.where(big, limit * tau / np.where(big, np.abs(tau), 1.0), tau)
             t2 = tt.copy()
