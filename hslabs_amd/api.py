@@ -31,6 +31,34 @@ def _require(ok: bool, msg: str) -> None:
     if not ok:
         raise ValueError(msg)
 
+
+def _torch_stream(device, stream):
+    """``stream``, or torch's current stream on ``device``"""
+    import torch
+
+    return stream if stream is not None else torch.cuda.current_stream(device)
+
+
+def _cuda_stream(device, stream):
+    """the HIP stream handle the native calls take"""
+    return _torch_stream(device, stream).cuda_stream
+
+
+def _precision(dtype) -> int:
+    """torch.float64 / torch.float32 -> HS_PREC_F64 / HS_PREC_F32"""
+    import torch
+
+    _require(dtype in (torch.float64, torch.float32), f"dtype must be torch.float64 or torch.float32, got {dtype}")
+    return capi.HS_PREC_F32 if dtype == torch.float32 else capi.HS_PREC_F64
+
+
+def _out_shapes(dims, B: int, H: int) -> dict:
+    """shapes of the batched path's outputs for B rollouts of H steps (dims: a model or hs_model_dims)"""
+    return {"q": (B, H, dims.config_dim), "dq": (B, H, dims.config_dim), "tau": (B, H, dims.nmj),
+            "cf": (B, H, 3 * dims.nfeet), "x": (B, H, 6 * dims.n_parts), "flags": (B, H), "work_cot": (B, 2),
+            "work": (B,), "cot": (B,)}
+
+
 SWEEP_NAMES = ("step_duration", "period", "step_length", "step_height")  # pergen.cpp:423
 
 
@@ -245,14 +273,9 @@ def run_host(model: KinematicModel, params, n_t: int = 20, k0: int = 0, horizon:
     arr = params_array(params)
     B = len(arr)
     H = n_t if horizon is None else horizon
-    out = {
-        "q": np.zeros((B, H, model.config_dim)) if "q" in want else None,
-        "tau": np.zeros((B, H, model.nmj)) if "tau" in want else None,
-        "cf": np.zeros((B, H, 3 * model.nfeet)) if "cf" in want else None,
-        "x": np.zeros((B, H, 6 * model.n_parts)) if "x" in want else None,
-        "flags": np.zeros((B, H), np.uint32) if "flags" in want else None,
-        "work_cot": np.zeros((B, 2)) if "work_cot" in want else None,
-    }
+    shapes = _out_shapes(model, B, H)
+    out = {k: np.zeros(shapes[k], np.uint32 if k == "flags" else np.float64) if k in want else None
+           for k in ("q", "tau", "cf", "x", "flags", "work_cot")}
     dp = ctypes.POINTER(ctypes.c_double)
 
     def P(a, t=dp):
@@ -286,9 +309,8 @@ class ShardedBatch:
                    "hs_batch_set_params")
 
     def _shapes(self) -> dict:
-        m, B, H = self.model, self.B, self.H
-        return {"q": (B, H, m.config_dim), "tau": (B, H, m.nmj), "cf": (B, H, 3 * m.nfeet),
-                "x": (B, H, 6 * m.n_parts), "flags": (B, H), "work": (B,), "cot": (B,)}
+        shapes = _out_shapes(self.model, self.B, self.H)
+        return {k: shapes[k] for k, _ in capi.BatchOutputsC._fields_}
 
     def run(self, k0: int = 0, ignore_reach: bool = True, want=("tau", "cf", "flags", "work", "cot")) -> dict:
         shapes = self._shapes()
@@ -360,10 +382,8 @@ class Comm:
 
     def reduce_best(self, key, stream=None) -> None:
         """In-place all-reduce(MIN) of a device key tensor (int64 [1] holding the uint64 bits)."""
-        import torch
-
-        st = stream if stream is not None else torch.cuda.current_stream(key.device)
-        capi.check(capi.load().hs_comm_reduce_best(self.handle, key.data_ptr(), st.cuda_stream), "hs_comm_reduce_best")
+        capi.check(capi.load().hs_comm_reduce_best(self.handle, key.data_ptr(), _cuda_stream(key.device, stream)),
+                   "hs_comm_reduce_best")
 
     def free(self) -> None:
         if self.handle:
@@ -404,18 +424,12 @@ class DeviceBatch:
         dev = device or torch.device("cuda", torch.cuda.current_device())
         self.device = dev
         self.dtype = dtype or torch.float64
-        assert self.dtype in (torch.float64, torch.float32)
-        self.precision = capi.HS_PREC_F32 if self.dtype == torch.float32 else capi.HS_PREC_F64
+        self.precision = _precision(self.dtype)
         self.params = torch.from_numpy(arr.view(np.uint8).copy()).to(dev)
-        f64 = dict(dtype=self.dtype, device=dev)
-        B, H = self.B, self.H
-        self.q = torch.empty((B, H, dims.config_dim), **f64) if "q" in outputs else None
-        self.dq = torch.empty((B, H, dims.config_dim), **f64) if "dq" in outputs else None
-        self.tau = torch.empty((B, H, dims.nmj), **f64) if "tau" in outputs else None
-        self.cf = torch.empty((B, H, 3 * dims.nfeet), **f64) if "cf" in outputs else None
-        self.x = torch.empty((B, H, 6 * dims.n_parts), **f64) if "x" in outputs else None
-        self.flags = torch.empty((B, H), dtype=torch.int32, device=dev) if "flags" in outputs else None
-        self.work_cot = torch.empty((B, 2), **f64) if "work_cot" in outputs else None
+        shapes = _out_shapes(dims, self.B, self.H)
+        for k in ("q", "dq", "tau", "cf", "x", "flags", "work_cot"):
+            setattr(self, k, torch.empty(shapes[k], dtype=torch.int32 if k == "flags" else self.dtype, device=dev)
+                    if k in outputs else None)
         self.best_key = torch.full((1,), -1, dtype=torch.int64, device=dev)  # UINT64_MAX bit pattern
         self.solve_mode = capi.HS_SOLVE_AUTO  # HS_SOLVE_REFERENCE: every step through the Eigen-style path
         self.key_steps = 0  # steps the best key's work covers (0: those of the call)
@@ -424,7 +438,6 @@ class DeviceBatch:
         self.best_key.fill_(-1)
 
     def _args(self, stream, best: bool, accumulate: bool):
-        torch = self.torch
         a = capi.RunArgsC()
         a.n_rollouts, a.horizon, a.k0, a.n_t = self.B, self.H, self.k0, self.n_t
         a.ignore_reach = int(self.ignore_reach)
@@ -441,8 +454,7 @@ class DeviceBatch:
         a.precision = self.precision
         a.solve_mode = self.solve_mode
         a.key_steps = self.key_steps
-        st = stream if stream is not None else torch.cuda.current_stream(self.device)
-        a.stream = st.cuda_stream
+        a.stream = _cuda_stream(self.device, stream)
         return a
 
     def _launch(self, a, n_calls, ev):
@@ -476,38 +488,35 @@ class DeviceBatch:
         """Contact forces of all feet given motor torques (hs_run_forces,
         forcetorquesolver::solve_forces): tau_in is a device tensor [B][H][nmj]; writes
         self.cf (and q / flags if allocated)."""
-        t = tau_in.to(dtype=self.dtype, device=self.device).contiguous()
-        _require(t.shape == (self.B, self.H, self.model.nmj), f"tau_in must be {(self.B, self.H, self.model.nmj)}")
-        a = self._args(stream, False, False)
-        a.tau = a.x = a.work_cot = None
+        a, t = self._forces_call(tau_in, self.H, self.H, stream)
         capi.check(capi.load().hs_run_forces(self.model.handle, ctypes.byref(a), t.data_ptr()), "hs_run_forces")
         self._tau_in = t  # keep alive until the stream has consumed it
+
+    def _forces_call(self, tau_in, n_steps: int, call_horizon: int, stream):
+        """(args, torques) of a solve_forces call: tau_in as a contiguous [B][n_steps][nmj] tensor of the
+        batch's dtype on its device, the run arguments without tau / x / work_cot at the call's horizon"""
+        t = tau_in.to(dtype=self.dtype, device=self.device).contiguous()
+        shape = (self.B, n_steps, self.model.nmj)
+        _require(t.shape == shape, f"tau_in must be {shape}")
+        a = self._args(stream, False, False)
+        a.tau = a.x = a.work_cot = None
+        a.horizon = call_horizon
+        return a, t
 
     def run_forces_calls(self, tau_in, n_calls: int, call_horizon: int = 1, stream=None) -> None:
         """n_calls calls of run_forces with call horizon ``call_horizon`` fused into few launches
         (hs_run_forces_calls): tau_in is a device tensor [B][S][nmj] with S = n_calls *
         call_horizon = this batch's horizon; every step writes its own row of cf (and q / flags)."""
-        S = n_calls * call_horizon
-        _require(self.H == S, "the batch's horizon must equal n_calls * call_horizon (one row per step)")
-        t = tau_in.to(dtype=self.dtype, device=self.device).contiguous()
-        _require(t.shape == (self.B, S, self.model.nmj), f"tau_in must be {(self.B, S, self.model.nmj)}")
-        a = self._args(stream, False, False)
-        a.tau = a.x = a.work_cot = None
-        a.horizon = call_horizon
-        capi.check(capi.load().hs_run_forces_calls(self.model.handle, ctypes.byref(a), n_calls, t.data_ptr()),
-                   "hs_run_forces_calls")
-        self._tau_in = t
+        launch = self.forces_launcher(tau_in, n_calls, call_horizon, stream)
+        launch()
+        self._tau_in = launch.tau_in
 
     def forces_launcher(self, tau_in, n_calls: int, call_horizon: int = 1, stream=None):
         """run_forces_calls(...) with its arguments resolved once: a no-argument callable that only
         enqueues the fused launches (bench.py --forces' timed loop)."""
         S = n_calls * call_horizon
         _require(self.H == S, "the batch's horizon must equal n_calls * call_horizon (one row per step)")
-        t = tau_in.to(dtype=self.dtype, device=self.device).contiguous()
-        _require(t.shape == (self.B, S, self.model.nmj), f"tau_in must be {(self.B, S, self.model.nmj)}")
-        a = self._args(stream, False, False)
-        a.tau = a.x = a.work_cot = None
-        a.horizon = call_horizon
+        a, t = self._forces_call(tau_in, S, call_horizon, stream)
         L = capi.load()
         ref, h, ptr = ctypes.byref(a), self.model.handle, t.data_ptr()
 
@@ -527,13 +536,16 @@ class DeviceBatch:
         ev = None
         if events is not None:
             _require(len(events) == 2 * n_calls, "events must hold 2 * n_calls events")
-            st = stream if stream is not None else self.torch.cuda.current_stream(self.device)
+            st = _torch_stream(self.device, stream)
             for e in events:  # torch creates the HIP event on first record
                 if not e.cuda_event:
                     e.record(st)
             ev = (ctypes.c_void_p * len(events))(*[e.cuda_event for e in events])
         self._launch(a, n_calls, ev)
 
+    def _calls_entry(self):
+        """(function, handle, name) of the fused-calls entry point of this kind of batch"""
+        return capi.load().hs_run_calls, self.model.handle, "hs_run_calls"
 
     def calls_launcher(self, n_calls: int, call_horizon: int = 1, stream=None, best: bool = False,
                        accumulate: bool = True):
@@ -542,12 +554,8 @@ class DeviceBatch:
         _require(self.H >= n_calls * call_horizon, "outputs need one row per fused step")
         a = self._args(stream, best, accumulate)
         a.horizon = call_horizon
-        L = capi.load()
         ref = ctypes.byref(a)
-        if isinstance(self, MixedBatch):
-            fn, h, what = L.hs_run_mixed_calls, self.plan, "hs_run_mixed_calls"
-        else:
-            fn, h, what = L.hs_run_calls, self.model.handle, "hs_run_calls"
+        fn, h, what = self._calls_entry()
 
         def launch():
             rc = fn(h, ref, n_calls)
@@ -562,14 +570,10 @@ class DeviceBatch:
         fused into few launches (hs_run_calls): every step keeps its own output row, rows packed
         per rollout with stride n_calls * call_horizon, so this batch's horizon must be at least
         that (equal: the [B][H] views hold the steps in order)."""
-        _require(self.H >= n_calls * call_horizon, "outputs need one row per fused step")
-        a = self._args(stream, best, accumulate)
-        a.horizon = call_horizon
-        L = capi.load()
-        if isinstance(self, MixedBatch):
-            capi.check(L.hs_run_mixed_calls(self.plan, ctypes.byref(a), n_calls), "hs_run_mixed_calls")
-        else:
-            capi.check(L.hs_run_calls(self.model.handle, ctypes.byref(a), n_calls), "hs_run_calls")
+        self.calls_launcher(n_calls, call_horizon, stream, best, accumulate)()
+
+
+SIM_STEP_OUTPUTS = ("tau_cmd", "q_meas", "torso", "n_contacts", "normal_force")  # hs_sim_args' per-step outputs
 
 
 class SimBatch:
@@ -610,8 +614,10 @@ class SimBatch:
         dev = device or torch.device("cuda", torch.cuda.current_device())
         self.device = dev
         self.dtype = dtype or torch.float64
-        assert self.dtype in (torch.float64, torch.float32)
-        self.precision = capi.HS_PREC_F32 if self.dtype == torch.float32 else capi.HS_PREC_F64
+        self.precision = _precision(self.dtype)
+        self.state = self.fall_z = None  # the trial state, made by the first trial() / cpc_step()
+        self.low_tpdist = self.last_tpi = self.cpc_flags = None  # the CPC controller's, made by _cpc_state()
+        self._tp = None  # cpc_target_points(), built on first use
         self.tables = DeviceBatch(model, arr, n_t=self.n_t, k0=0, horizon=self.n_t, ignore_reach=ignore_reach,
                                   outputs=("q", "dq", "tau"), device=dev, dtype=self.dtype)
         self.tables.run(best=False)
@@ -634,51 +640,98 @@ class SimBatch:
         """init_play_config (player.cpp:351-356): bodies at trajectory sample tsi0, at rest."""
         torch = self.torch
         config = self.tables.q[:, self.table_row(tsi0), :].contiguous()
-        st = stream if stream is not None else torch.cuda.current_stream(self.device)
         capi.check(capi.load().hs_sim_reset(self.model.handle, self.B, config.data_ptr(), config.shape[1],
-                                            self.body.data_ptr(), self.precision, st.cuda_stream), "hs_sim_reset")
+                                            self.body.data_ptr(), self.precision,
+                                            _cuda_stream(self.device, stream)), "hs_sim_reset")
         self._config = config
         self.seed.zero_()
         self.tsi.fill_(int(tsi0))
         # the derivative tracker (configtimedertrack: zeros at construction) and the last motor torques
         self.ders = torch.zeros((self.B, 3, self.model.config_dim), dtype=torch.float64, device=self.device)
         self.last_tau = None
-        if getattr(self, "low_tpdist", None) is not None:  # the CPC controller's carried state (cpc.cpp:35, 42)
+        if self.low_tpdist is not None:  # the CPC controller's carried state (cpc.cpp:35, 42)
             self.low_tpdist.fill_(1)
             self.last_tpi.zero_()
 
-    def step(self, n_steps: int = 1, stream=None, outputs=("tau_cmd", "q_meas", "torso", "n_contacts",
-                                                           "normal_force")) -> dict:
+    def step(self, n_steps: int = 1, stream=None, outputs=SIM_STEP_OUTPUTS) -> dict:
         """n_steps of simulate_ode for every rollout (one launch). Returns the requested
         per-step outputs as device tensors [B][n_steps][...]."""
-        torch = self.torch
-        B, nmj = self.B, self.model.nmj
-        f64 = dict(dtype=self.dtype, device=self.device)
-        out = {}
-        if "tau_cmd" in outputs:
-            out["tau_cmd"] = torch.empty((B, n_steps, nmj), **f64)
-        if "q_meas" in outputs:
-            out["q_meas"] = torch.empty((B, n_steps, nmj), **f64)
-        if "torso" in outputs:
-            out["torso"] = torch.empty((B, n_steps, 3), **f64)
-        if "n_contacts" in outputs:
-            out["n_contacts"] = torch.empty((B, n_steps), dtype=torch.int32, device=self.device)
-        if "normal_force" in outputs:
-            out["normal_force"] = torch.empty((B, n_steps), **f64)
+        wanted = dict.fromkeys([k for k in SIM_STEP_OUTPUTS if k in outputs], True)
+        out = self._step_outputs(n_steps, wanted, fill=False)
         a = capi.SimArgsC()
-        a.n_rollouts, a.n_steps, a.n_t = B, n_steps, self.n_t
-        a.precision = self.precision
-        a.params = self.params
-        a.body, a.seed, a.tsi = self.body.data_ptr(), self.seed.data_ptr(), self.tsi.data_ptr()
-        a.q_tab, a.dq_tab, a.tau_tab = self.tables.q.data_ptr(), self.tables.dq.data_ptr(), self.tables.tau.data_ptr()
-        for k in ("tau_cmd", "q_meas", "torso", "n_contacts", "normal_force"):
-            setattr(a, k, out[k].data_ptr() if k in out else None)
-        st = stream if stream is not None else torch.cuda.current_stream(self.device)
-        a.stream = st.cuda_stream
+        self._sim_args(a, n_steps, self.n_t, out, stream)
         capi.check(capi.load().hs_sim_step(self.model.handle, ctypes.byref(a)), "hs_sim_step")
         if "tau_cmd" in out and n_steps > 0:
             self.last_tau = out["tau_cmd"][:, -1, :]
         return out
+
+    def _step_shapes(self, n_steps: int, step_major: bool = False) -> dict:
+        """shapes of the five per-step outputs: rows [B][n_steps], or [n_steps][B] (cpc_step's) if step_major"""
+        rows, nmj = ((n_steps, self.B) if step_major else (self.B, n_steps)), self.model.nmj
+        return {"tau_cmd": rows + (nmj,), "q_meas": rows + (nmj,), "torso": rows + (3,), "n_contacts": rows,
+                "normal_force": rows}
+
+    def _step_outputs(self, n_steps: int, requests: dict, step_major: bool = False, fill: bool = True) -> dict:
+        """The per-step output tensors of ``requests`` (name -> True: a fresh tensor; a tensor: that one,
+        checked; False / None: not wanted). Fresh tensors hold NaN (-1 in n_contacts) for the rows a frozen
+        rollout does not reach; fill=False leaves them uninitialised (step() writes every row)."""
+        torch = self.torch
+        shapes = self._step_shapes(n_steps, step_major)
+        res = {}
+        for k, v in requests.items():
+            if k not in shapes:
+                raise TypeError(f"unknown output {k}")
+            if v is False or v is None:
+                continue
+            want = torch.int32 if k == "n_contacts" else self.dtype
+            if v is not True:
+                if tuple(v.shape) != shapes[k] or v.dtype != want or not v.is_contiguous():
+                    raise ValueError(f"output {k}: need a contiguous {want} tensor of shape {shapes[k]}")
+                res[k] = v
+            elif fill:
+                res[k] = torch.full(shapes[k], -1 if k == "n_contacts" else float("nan"), dtype=want,
+                                    device=self.device)
+            else:
+                res[k] = torch.empty(shapes[k], dtype=want, device=self.device)
+        return res
+
+    def _sim_args(self, a, n_steps: int, n_t: int, out: dict, stream, tables: bool = True) -> None:
+        """fills the hs_sim_args ``a``: the batch's state, its controller tables of length n_t (tables=False:
+        none, cpc_step's torques come from the controller), the per-step outputs in ``out`` and the stream"""
+        a.n_rollouts, a.n_steps, a.n_t = self.B, n_steps, n_t
+        a.precision = self.precision
+        a.params = self.params
+        a.body, a.seed, a.tsi = self.body.data_ptr(), self.seed.data_ptr(), self.tsi.data_ptr()
+        tabs = self.tables
+        a.q_tab, a.dq_tab, a.tau_tab = (tabs.q.data_ptr(), tabs.dq.data_ptr(), tabs.tau.data_ptr()) if tables else \
+            (None, None, None)
+        for k in SIM_STEP_OUTPUTS:
+            setattr(a, k, out[k].data_ptr() if k in out else None)
+        a.stream = _cuda_stream(self.device, stream)
+
+    def _trial_state(self) -> None:
+        """``self.state`` / ``self.fall_z`` on first use: every rollout running, no fall seen"""
+        if self.state is None:
+            torch = self.torch
+            self.state = torch.full((self.B,), capi.HS_TRIAL_RUNNING, dtype=torch.int32, device=self.device)
+            self.fall_z = torch.full((self.B,), float("nan"), dtype=self.dtype, device=self.device)
+
+    def _trial_args(self, t, open_loop, torque_limit, kick_every, kick_phase, kick_dv, hc, check_from,
+                    check_until) -> None:
+        """fills what hs_sim_trial_args ``t`` holds beyond its hs_sim_args (trial()'s keywords)"""
+        t.open_loop = 1 if open_loop else 0
+        t.torque_limit = float(torque_limit)
+        t.kick_every = int(kick_every)
+        t.kick_phase = int(kick_every) - 1 if kick_phase is None else int(kick_phase)
+        if kick_dv is not None:
+            dv = self.torch.as_tensor(kick_dv, dtype=self.dtype, device=self.device).contiguous()
+            if tuple(dv.shape) != (self.B, 3):
+                raise ValueError(f"kick_dv: need [B][3] = {(self.B, 3)}, got {tuple(dv.shape)}")
+            self._kick_dv = dv  # alive until the launch has run
+            t.kick_dv = dv.data_ptr()
+        t.hc = float(hc)
+        t.check_from, t.check_until = int(check_from), int(check_until)
+        t.state, t.fall_z = self.state.data_ptr(), self.fall_z.data_ptr()
 
     def trial(self, n_steps: int, *, open_loop: bool = False, torque_limit: float = 0.0, kick_every: int = 0,
               kick_phase: int | None = None, kick_dv=None, hc: float = 0.0, check_from: int = 0,
@@ -693,55 +746,11 @@ class SimBatch:
         per-step outputs, named as keywords (``torso=True``: a fresh tensor; ``torso=tensor``: that
         tensor; none named: all five, as step()). Rows a frozen rollout did not reach keep what they
         held (NaN in fresh floating-point tensors, -1 in n_contacts)."""
-        torch = self.torch
-        B, nmj = self.B, self.model.nmj
-        if not hasattr(self, "state"):
-            self.state = torch.full((B,), capi.HS_TRIAL_RUNNING, dtype=torch.int32, device=self.device)
-            self.fall_z = torch.full((B,), float("nan"), dtype=self.dtype, device=self.device)
-        shapes = {"tau_cmd": (B, n_steps, nmj), "q_meas": (B, n_steps, nmj), "torso": (B, n_steps, 3),
-                  "n_contacts": (B, n_steps), "normal_force": (B, n_steps)}
-        if not outputs:
-            outputs = dict.fromkeys(shapes, True)
-        res = {}
-        for k, v in outputs.items():
-            if k not in shapes:
-                raise TypeError(f"unknown output {k}")
-            if v is False or v is None:
-                continue
-            if v is not True:
-                res[k] = v
-            elif k == "n_contacts":
-                res[k] = torch.full(shapes[k], -1, dtype=torch.int32, device=self.device)
-            else:
-                res[k] = torch.full(shapes[k], float("nan"), dtype=self.dtype, device=self.device)
-        for k, v in res.items():
-            want = torch.int32 if k == "n_contacts" else self.dtype
-            if tuple(v.shape) != shapes[k] or v.dtype != want or not v.is_contiguous():
-                raise ValueError(f"output {k}: need a contiguous {want} tensor of shape {shapes[k]}")
+        self._trial_state()
+        res = self._step_outputs(n_steps, outputs or dict.fromkeys(SIM_STEP_OUTPUTS, True))
         t = capi.SimTrialArgsC()
-        a = t.sim
-        a.n_rollouts, a.n_steps, a.n_t = B, n_steps, self.n_t
-        a.precision = self.precision
-        a.params = self.params
-        a.body, a.seed, a.tsi = self.body.data_ptr(), self.seed.data_ptr(), self.tsi.data_ptr()
-        a.q_tab, a.dq_tab, a.tau_tab = self.tables.q.data_ptr(), self.tables.dq.data_ptr(), self.tables.tau.data_ptr()
-        for k in shapes:
-            setattr(a, k, res[k].data_ptr() if k in res else None)
-        st = stream if stream is not None else torch.cuda.current_stream(self.device)
-        a.stream = st.cuda_stream
-        t.open_loop = 1 if open_loop else 0
-        t.torque_limit = float(torque_limit)
-        t.kick_every = int(kick_every)
-        t.kick_phase = int(kick_every) - 1 if kick_phase is None else int(kick_phase)
-        if kick_dv is not None:
-            dv = torch.as_tensor(kick_dv, dtype=self.dtype, device=self.device).contiguous()
-            if tuple(dv.shape) != (B, 3):
-                raise ValueError(f"kick_dv: need [B][3] = {(B, 3)}, got {tuple(dv.shape)}")
-            self._kick_dv = dv  # alive until the launch has run
-            t.kick_dv = dv.data_ptr()
-        t.hc = float(hc)
-        t.check_from, t.check_until = int(check_from), int(check_until)
-        t.state, t.fall_z = self.state.data_ptr(), self.fall_z.data_ptr()
+        self._sim_args(t.sim, n_steps, self.n_t, res, stream)
+        self._trial_args(t, open_loop, torque_limit, kick_every, kick_phase, kick_dv, hc, check_from, check_until)
         capi.check(capi.load().hs_sim_trial(self.model.handle, ctypes.byref(t)), "hs_sim_trial")
         res["state"], res["fall_z"] = self.state, self.fall_z
         if "tau_cmd" in res and n_steps > 0:
@@ -749,10 +758,6 @@ class SimBatch:
         return res
 
     # ---- dynamics from simulation (estimate_B_by_regression, player.cpp:548-582)
-
-    def _stream(self, stream):
-        st = stream if stream is not None else self.torch.cuda.current_stream(self.device)
-        return st.cuda_stream
 
     def config(self, body=None, stream=None):
         """visualizer::get_ode_config of every rollout (hs_sim_config): [B][config_dim] = torso
@@ -766,7 +771,7 @@ class SimBatch:
         n = int(np.prod(lead)) if lead else 1
         cfg = torch.empty(lead + (self.model.config_dim,), dtype=self.dtype, device=self.device)
         capi.check(capi.load().hs_sim_config(self.model.handle, n, body.data_ptr(), cfg.data_ptr(),
-                                             self.model.config_dim, self.precision, self._stream(stream)),
+                                             self.model.config_dim, self.precision, _cuda_stream(self.device, stream)),
                    "hs_sim_config")
         return cfg
 
@@ -780,7 +785,7 @@ class SimBatch:
                  "config: [B][config_dim]")
         capi.check(capi.load().hs_sim_track_push(self.model.handle, self.B, config.data_ptr(), config.shape[1],
                                                  float(self.params.dt), self.ders.data_ptr(), self.precision,
-                                                 self._stream(stream)), "hs_sim_track_push")
+                                                 _cuda_stream(self.device, stream)), "hs_sim_track_push")
         return self.ders
 
     def _tau0(self, tau0):
@@ -812,7 +817,7 @@ class SimBatch:
         a.dtau = dtau.data_ptr()
         for k in ("config_out", "tau_out", "body_out", "n_contacts"):
             setattr(a, k, res[k].data_ptr() if k in res else None)
-        a.stream = self._stream(stream)
+        a.stream = _cuda_stream(self.device, stream)
         return res, (dtau, t0)  # the inputs stay alive with the caller until the launch is enqueued
 
     def probe(self, dtau, tau0=None, stream=None, body_out=False, n_contacts=False) -> dict:
@@ -870,7 +875,7 @@ class SimBatch:
                "rank": torch.empty((B,), dtype=torch.int32, device=self.device)}
         capi.check(capi.load().hs_sim_regress_B(self.model.handle, B, int(T.shape[1]), T.data_ptr(), U.data_ptr(),
                                                 res["Bt"].data_ptr(), res["rank"].data_ptr(), capi.HS_PREC_F64,
-                                                self._stream(stream)), "hs_sim_regress_B")
+                                                _cuda_stream(self.device, stream)), "hs_sim_regress_B")
         return res
 
     # ---- configuration path control (cpccontroller, cpc.cpp; player.cpp:440-481)
@@ -893,7 +898,8 @@ class SimBatch:
         tp = torch.empty((self.B, self.n_t, 2 * cfg + nmj), dtype=torch.float64, device=self.device)
         capi.check(capi.load().hs_cpc_target_points(self.model.handle, self.B, self.n_t, self.tables.q.data_ptr(),
                                                     self.tables.dq.data_ptr(), self.tables.tau.data_ptr(), mask,
-                                                    tp.data_ptr(), self._stream(stream)), "hs_cpc_target_points")
+                                                    tp.data_ptr(), _cuda_stream(self.device, stream)),
+                   "hs_cpc_target_points")
         return tp
 
     def _cpc_tp(self, tp):
@@ -902,7 +908,7 @@ class SimBatch:
         torch = self.torch
         rec = 2 * self.model.config_dim + self.model.nmj
         if tp is None:
-            if getattr(self, "_tp", None) is None:
+            if self._tp is None:
                 self._tp = self.cpc_target_points()
             tp = self._tp
         tp = torch.as_tensor(tp, dtype=torch.float64, device=self.device).contiguous()
@@ -913,7 +919,7 @@ class SimBatch:
 
     def _cpc_state(self):
         torch = self.torch
-        if getattr(self, "low_tpdist", None) is None:
+        if self.low_tpdist is None:
             self.low_tpdist = torch.ones((self.B,), dtype=torch.int32, device=self.device)  # cpc.cpp:42
             self.last_tpi = torch.zeros((self.B,), dtype=torch.int32, device=self.device)
             self.cpc_flags = torch.zeros((self.B,), dtype=torch.int32, device=self.device)
@@ -956,7 +962,7 @@ class SimBatch:
         a.last_tpi, a.flags = self.last_tpi.data_ptr(), self.cpc_flags.data_ptr()
         for k in shapes:
             setattr(a, k, res[k].data_ptr() if k in res else None)
-        a.stream = self._stream(stream)
+        a.stream = _cuda_stream(self.device, stream)
         capi.check(capi.load().hs_cpc_torques(self.model.handle, ctypes.byref(a)), "hs_cpc_torques")
         res.update(last_tpi=self.last_tpi, flags=self.cpc_flags, low_tpdist=self.low_tpdist)
         return res
@@ -989,41 +995,14 @@ class SimBatch:
         m = int(dtau.shape[-2])
         tp, n_tp, tp_stride = self._cpc_tp(tp)
         self._cpc_state()
-        if not hasattr(self, "state"):
-            self.state = torch.full((B,), capi.HS_TRIAL_RUNNING, dtype=torch.int32, device=self.device)
-            self.fall_z = torch.full((B,), float("nan"), dtype=self.dtype, device=self.device)
+        self._trial_state()
         tau0 = self._tau0(None)
         tau0 = torch.zeros((B, nmj), dtype=torch.float64, device=self.device) if tau0 is None else tau0.clone()
-        shapes = {"tau_cmd": (n_steps, B, nmj), "q_meas": (n_steps, B, nmj), "torso": (n_steps, B, 3),
-                  "n_contacts": (n_steps, B), "normal_force": (n_steps, B)}
-        res = {}
-        for k, v in outputs.items():
-            if k not in shapes:
-                raise TypeError(f"unknown output {k}")
-            if v:
-                res[k] = torch.full(shapes[k], -1, dtype=torch.int32, device=self.device) if k == "n_contacts" else \
-                    torch.full(shapes[k], float("nan"), dtype=torch.float64, device=self.device)
+        res = self._step_outputs(n_steps, {k: bool(v) for k, v in outputs.items()}, step_major=True)
         L = capi.load()
         c = capi.SimCpcArgsC()
-        t = c.trial
-        a = t.sim
-        a.n_rollouts, a.n_steps, a.n_t, a.precision, a.params = B, int(n_steps), 1, self.precision, self.params
-        a.body, a.seed, a.tsi = self.body.data_ptr(), self.seed.data_ptr(), self.tsi.data_ptr()
-        for k in shapes:
-            setattr(a, k, res[k].data_ptr() if k in res else None)
-        a.stream = self._stream(stream)
-        t.open_loop = 1
-        t.torque_limit = float(torque_limit)
-        t.kick_every = int(kick_every)
-        t.kick_phase = int(kick_every) - 1 if kick_phase is None else int(kick_phase)
-        if kick_dv is not None:
-            dv = torch.as_tensor(kick_dv, dtype=self.dtype, device=self.device).contiguous()
-            _require(tuple(dv.shape) == (B, 3), "kick_dv: [B][3]")
-            self._kick_dv = dv
-            t.kick_dv = dv.data_ptr()
-        t.hc = float(hc)
-        t.check_from, t.check_until = int(check_from), int(check_until)
-        t.state, t.fall_z = self.state.data_ptr(), self.fall_z.data_ptr()
+        self._sim_args(c.trial.sim, int(n_steps), 1, res, stream, tables=False)
+        self._trial_args(c.trial, True, torque_limit, kick_every, kick_phase, kick_dv, hc, check_from, check_until)
         c.cpc, c.m, c.n_tp = P, m, n_tp
         c.dtau, c.dtau_step_stride = dtau.data_ptr(), (B * m * nmj if dtau.dim() == 4 else 0)
         c.tp, c.tp_stride = tp.data_ptr(), tp_stride
@@ -1053,19 +1032,17 @@ class SimBatch:
 
     def trial_reset(self) -> None:
         """Every rollout RUNNING again (after reset())."""
-        if hasattr(self, "state"):
+        if self.state is not None:
             self.state.fill_(capi.HS_TRIAL_RUNNING)
             self.fall_z.fill_(float("nan"))
 
     def trial_summary(self, stream=None) -> dict:
         """hs_sim_trial_summary of ``self.state``: counts, and the minimum (-1: none) and sum of the fall tsi."""
-        torch = self.torch
-        if not hasattr(self, "state"):
+        if self.state is None:
             raise capi.HSError("trial_summary: no trial has run")
-        st = stream if stream is not None else torch.cuda.current_stream(self.device)
         o = capi.TrialSummaryC()
-        capi.check(capi.load().hs_sim_trial_summary(self.state.data_ptr(), self.B, ctypes.byref(o), st.cuda_stream),
-                   "hs_sim_trial_summary")
+        capi.check(capi.load().hs_sim_trial_summary(self.state.data_ptr(), self.B, ctypes.byref(o),
+                                                    _cuda_stream(self.device, stream)), "hs_sim_trial_summary")
         return {k: int(getattr(o, k)) for k in ("running", "survived", "fallen", "min_fall_tsi", "sum_fall_tsi")}
 
 
@@ -1100,6 +1077,9 @@ class MixedBatch(DeviceBatch):
 
     def _launch(self, a, n_calls, ev):
         capi.check(capi.load().hs_run_mixed_steps(self.plan, ctypes.byref(a), n_calls, ev), "hs_run_mixed_steps")
+
+    def _calls_entry(self):
+        return capi.load().hs_run_mixed_calls, self.plan, "hs_run_mixed_calls"
 
     def __del__(self):
         plan = getattr(self, "plan", None)

@@ -195,6 +195,17 @@ class TrialSummaryC(ctypes.Structure):
                 ("min_fall_tsi", ctypes.c_int32), ("sum_fall_tsi", ctypes.c_int64)]
 
 
+# every struct of include/hslabs.h and its mirror above; tests/test_capi_layout.py holds each mirror's
+# size and field offsets to the header's, and this table to the header's list of structs
+C_STRUCTS = {
+    "hs_gait_params": GaitParamsC, "hs_model_dims": ModelDimsC, "hs_node_info": NodeInfoC, "hs_run_args": RunArgsC,
+    "hs_pd_args": PdArgsC, "hs_batch_outputs": BatchOutputsC, "hs_sim_params": SimParamsC, "hs_sim_args": SimArgsC,
+    "hs_sim_trial_args": SimTrialArgsC, "hs_trial_summary": TrialSummaryC, "hs_sim_probe_args": SimProbeArgsC,
+    "hs_sim_estimate_args": SimEstimateArgsC, "hs_cpc_params": CpcParamsC, "hs_cpc_args": CpcArgsC,
+    "hs_sim_cpc_args": SimCpcArgsC,
+}
+
+
 class HSError(RuntimeError):
     pass
 

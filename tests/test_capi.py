@@ -179,6 +179,20 @@ def test_gait_record_layout(product):
     assert PgsConfigParams.from_record(p.to_record()) == p
 
 
+def test_dtype_maps_to_precision_or_is_refused(product):
+    """DeviceBatch / SimBatch take torch.float64 or torch.float32; anything else is a ValueError (not an
+    assert, which python -O drops: the kernels would then read a half tensor as doubles)"""
+    import torch
+
+    from hslabs_amd import api
+
+    assert api._precision(torch.float64) == product.capi.HS_PREC_F64
+    assert api._precision(torch.float32) == product.capi.HS_PREC_F32
+    for bad in (torch.float16, torch.int32, None):
+        with pytest.raises(ValueError, match="dtype must be"):
+            api._precision(bad)
+
+
 def test_sweep_values_follow_pgssweeper(product):
     # pergen.cpp:417-449: n_val+1 values val0 + vali*(val1-val0)/n_val
     sw = product.ModelPlayer.sweep_params(product.PgsConfigParams(), "period", 3, 18, 15)

@@ -481,3 +481,67 @@ def test_work_rounds_twice_bitwise(gpu, hmodels, path):
     if path == "fused":
         fma = _work_one_rounding(tau[:512], dq[:512], period[:512], 20, w0[:512])
         assert (fma != want[:512]).any(), "the one-rounding accumulation should differ somewhere"
+
+
+def _calls_batch(gpu, hmodels, kind, outputs):
+    """B = 64 rollouts, horizon 4 = 2 calls of call horizon 2, fp64: a DeviceBatch on hexapod, or a
+    MixedBatch of hexapod and spider rollouts interleaved"""
+    from hslabs_amd import synth
+
+    p = synth.gen_params(64, "hexapod", id0=31)
+    if kind == "device":
+        return gpu.DeviceBatch(hmodels["hexapod"], p, n_t=20, k0=3, horizon=4, outputs=outputs)
+    idx = (np.arange(64) % 2).astype(np.int32)
+    p[idx == 1] = synth.gen_params(64, "spider", id0=31)[idx == 1]
+    return gpu.MixedBatch([hmodels["hexapod"], hmodels["spider"]], idx, p, n_t=20, k0=3, horizon=4, outputs=outputs)
+
+
+@pytest.mark.parametrize("kind", ["device", "mixed"])
+def test_run_calls_equals_its_launcher(gpu, hmodels, kind):
+    """run_calls(...) and calls_launcher(...)() enqueue the same native call (hs_run_calls for a
+    DeviceBatch, hs_run_mixed_calls with the plan for a MixedBatch): the same bytes out."""
+    import torch
+
+    outs = ("tau", "cf", "flags", "work_cot")
+    got = []
+    for launcher in (False, True):
+        b = _calls_batch(gpu, hmodels, kind, outs)
+        b.work_cot.zero_()
+        for k in ("tau", "cf"):
+            getattr(b, k).fill_(float("nan"))
+        if launcher:
+            b.calls_launcher(2, call_horizon=2, best=True)()
+        else:
+            b.run_calls(2, call_horizon=2, best=True)
+        torch.cuda.synchronize()
+        got.append({k: npy(getattr(b, k)) for k in outs + ("best_key",)})
+    for k in got[0]:
+        assert got[0][k].tobytes() == got[1][k].tobytes(), k
+    for k in ("tau", "cf"):  # written over the NaN, by both models of the plan
+        assert np.isfinite(got[0][k][0::2]).any() and np.isfinite(got[0][k][1::2]).any(), k
+    if kind == "device":
+        assert np.isfinite(got[0]["tau"]).all() and np.isfinite(got[0]["cf"]).all()
+
+
+def test_run_forces_calls_equals_its_launcher(gpu, hmodels):
+    """run_forces_calls(...) and forces_launcher(...)() enqueue the same hs_run_forces_calls: the same
+    contact forces, bit for bit."""
+    import torch
+
+    ctl = _calls_batch(gpu, hmodels, "device", ("tau",))
+    ctl.run_calls(2, call_horizon=2)
+    tau = ctl.tau + 0.1 * torch.sin(torch.arange(ctl.tau.numel(), device=ctl.tau.device).reshape(ctl.tau.shape))
+    got = []
+    for launcher in (False, True):
+        b = _calls_batch(gpu, hmodels, "device", ("cf", "flags"))
+        b.cf.fill_(float("nan"))
+        if launcher:
+            b.forces_launcher(tau, 2, call_horizon=2)()
+        else:
+            b.run_forces_calls(tau, 2, call_horizon=2)
+            assert b._tau_in.data_ptr() == tau.data_ptr()  # kept alive on the batch, not copied
+        torch.cuda.synchronize()
+        got.append({k: npy(getattr(b, k)) for k in ("cf", "flags")})
+    assert got[0]["cf"].tobytes() == got[1]["cf"].tobytes()
+    assert np.array_equal(got[0]["flags"], got[1]["flags"])
+    assert np.isfinite(got[0]["cf"]).all()
