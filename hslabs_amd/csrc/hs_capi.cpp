@@ -798,6 +798,11 @@ int hs_run_pd(hs_model_t m, const hs_run_args* a, const hs_pd_args* pd) {
   });
   if (rc != HS_OK || cx.empty) return rc;
   hs::launch_map& mp = cx.map;
+  // get_motor_adas and get_computed_torques read the cycle at tsi mod n_t (periodic.cpp:396, periodic.h:51): step h
+  // of the call is the cycle's step (k0 + h) mod n_t (launch_rollouts), also where the call runs past the cycle's
+  // end -- one period later a turning gait's torques are not the cycle's. The samples are those of `horizon`
+  // calls of one step
+  hs::ktab_range(a->k0, a->n_t, 1, a->horizon, &mp.ktab_lo, &mp.ktab_n, &mp.ttab_n);
   mp.pd_q = pd->q_meas;
   mp.pd_dq = pd->dq_meas;
   mp.pd_k1 = -pd->k;                 // player.cpp:394

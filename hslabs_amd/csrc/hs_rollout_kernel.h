@@ -664,7 +664,8 @@ static int launch_rollouts(const hs_topo* d_topo, const hs_run_args& a, void* wo
   for (int h = 0; h < a.horizon; h++) {
     hs_run_args ah = a;
     launch_map mh = mp;
-    ah.k0 = a.k0 + h;
+    // position control reads the cycle at tsi mod n_t (hs_run_pd): its steps wrap within the call
+    ah.k0 = mp.pd_tau ? (int32_t)(((int64_t)a.k0 + h) % a.n_t) : a.k0 + h;
     ah.accumulate = (h == 0) ? a.accumulate : 1;
     if (h + 1 < a.horizon) ah.best_key = nullptr;
     mh.h_row = h;

@@ -1347,7 +1347,8 @@ __device__ inline void cross3(const real* a, const real* b, real* c) {
 //   (S + sum_f C~_f B_f^-1 C~_f^T) lam = sum_f C~_f B_f^-1 r_f - d~,   y_f = B_f^-1 (r_f - C~_f^T lam),
 // a 6 x 6 system (>= I); otherwise (a straight leg: B_f singular) N is formed and factorized as a
 // dense 3 nf x 3 nf Cholesky, pivot guard kFastPivotGuard: a pivot under it drops its force component
-// (HS_FLAG_GENERAL, the basic solution; chol_packed). Lanes: one per limb for the limb's blocks (M_l = L D L^T: every product Y_a^T D^-1 Y_b,
+// (HS_FLAG_GENERAL, the basic solution; chol_packed), followed by one step of the corrected semi-normal
+// equations, which takes the squared conditioning of N back out of the answer. Lanes: one per limb for the limb's blocks (M_l = L D L^T: every product Y_a^T D^-1 Y_b,
 // Y = L^-1 [W_mt | C_m | d_m]), one per packed entry for the sums over limbs (in limb order).
 constexpr real kForcesBlockGuard = HS_REAL_IS_FLOAT ? real(1e-3) : real(1e-6);
 constexpr int FSUM = 27;  // packed 6 x 6 lower triangle (21) + a 6-vector
@@ -1656,7 +1657,9 @@ __device__ __attribute__((always_inline)) inline uint32_t forces_solve(const hs_
   if (dropped) flags = HS_FLAG_GENERAL | HS_FLAG_DEPENDENT;  // least squares not unique: its basic solution
   if (rank_near) flags |= HS_FLAG_NEAR_RANK;
   STAMP(8);
-  if (lane == 0) {  // the two triangular solves with y in registers (nq <= HS_KMAX)
+  // the two triangular solves with the vector in registers (nq <= HS_KMAX): y = N^-1 rr (add = false), or
+  // y += N^-1 rr, a correction
+  auto solve_kept = [&](bool add) {
     real yv[HS_KMAX];
 #pragma unroll
     for (int i = 0; i < HS_KMAX; i++) yv[i] = (i < nq) ? rr[i] : real(0);
@@ -1681,7 +1684,56 @@ __device__ __attribute__((always_inline)) inline uint32_t forces_solve(const hs_
     }
 #pragma unroll
     for (int i = 0; i < HS_KMAX; i++)
-      if (i < nq) sv.y[i] = yv[i];
+      if (i < nq) sv.y[i] = add ? sv.y[i] + yv[i] : yv[i];
+  };
+  if (lane == 0) solve_kept(false);
+  wave_sync();
+  // One step of the corrected semi-normal equations. N = G^T G for G = [D_M^-1/2 Y_f per limb; D_S^-1/2 V], the
+  // least squares min |G y - g| with g = [D_M^-1/2 Y_d; D_S^-1/2 L_S^-1 d~]: forming N squares G's conditioning, so
+  // y above carries cond(N) eps. The residual g - G y from G's own entries (Y = L_M^-1 [C_m | d_m] recomputed from
+  // the limb's rows, V and L_S^-1 d~ as stored) costs no such squaring, and y += N^-1 G^T (g - G y) leaves
+  // cond(G) eps, as a QR of the system would, while cond(N) eps < 1. A dropped component stays 0.
+  {
+    real gl[3] = {0, 0, 0};
+    if (lane < nl) {
+      int p[3];
+      for (int k = 0; k < 3; k++) p[k] = T->limb_node[lane][k];
+      real J[3][3], Z[3][3], P[3][3], X[3][3], zz[3];
+      for (int k = 0; k < 3; k++) {
+        for (int t = 0; t < 3; t++) {
+          J[k][t] = w.jpos(0, p[k])[t];
+          Z[k][t] = w.jz(0, p[k])[t];
+          P[k][t] = w.pos(0, p[k])[t];
+          X[k][t] = sv.x[3 * n + 3 * p[k] + t];
+        }
+        zz[k] = z[T->node[p[k]].hinge];
+      }
+      ForcesRows F;
+      forces_rows(F, J, Z, P, w.fpos(0, f), P0, X, zz);
+      real e[3];
+      for (int k = 0; k < 3; k++) {
+        real s = F.R[k][9];
+        for (int jj = 0; jj < 3; jj++) s -= F.R[k][6 + jj] * sv.y[3 * f + jj];
+        e[k] = F.rdM[k] * s;
+      }
+      for (int jj = 0; jj < 3; jj++) gl[jj] = F.R[0][6 + jj] * e[0] + F.R[1][6 + jj] * e[1] + F.R[2][6 + jj] * e[2];
+    }
+    real u[6];  // D_S^-1 (L_S^-1 d~ - V y), by every lane
+    for (int k = 0; k < 6; k++) {
+      real s = vv[k];
+      for (int q = 0; q < nq; q++) s -= Vm[k * HS_KMAX + q] * sv.y[q];
+      u[k] = rdS[k] * s;
+    }
+    for (int q = lane; q < nq; q += HALF) {
+      real s = 0;
+      for (int k = 0; k < 6; k++) s += Vm[k * HS_KMAX + q] * u[k];
+      rr[q] = s;
+    }
+    wave_sync();
+    if (lane < nl)
+      for (int k = 0; k < 3; k++) rr[3 * f + k] += gl[k];
+    wave_sync();
+    if (lane == 0) solve_kept(true);
   }
   wave_sync();
   STAMP(9);

@@ -228,7 +228,10 @@ int hs_run_steps(hs_model_t model, const hs_run_args* args, int32_t n_calls, voi
  *   tau_cmd = tau_ff + (k1 * mod2pi(q - q0) + k2 * (dq - dq0)),
  *   k1 = -k, k2 = -2 sqrt(k), mod2pi into (-pi, pi] (arrayops::modulus).
  * The reference's step index tsi (mod n_t, lifted to [2, n_t + 1]) is the
- * centre sample: args->k0 = tsi - 2. All arrays DEVICE, [B][H][nmj]. */
+ * centre sample: args->k0 = tsi - 2. Step h of a call is the cycle's step
+ * (k0 + h) mod n_t: a call that runs past the cycle's end wraps, as tsi does
+ * (hs_run's steps do not wrap: one period later a turning gait's torques are
+ * not the cycle's). All arrays DEVICE, [B][H][nmj]. */
 typedef struct {
   const double* q_meas;   /* measured motor angles (get_ode_motor_adas) */
   const double* dq_meas;  /* measured motor rates */

@@ -1874,7 +1874,14 @@ bool solve_forces(const hso_model* m, const DynRec& d, const double* z, std::vec
     }
     b[6 * n + jj] = z[jj];
   }
-  const double kRankGuard = 1e-10;  // the kernel's kFastPivotGuard on the reduced normal matrix
+  // the kernel's kFastPivotGuard on the reduced normal matrix, of the build's precision: the single-precision
+  // build (hs_oracle_f32.cpp) takes the kernel's float value, 1e-10 being under float epsilon (no column
+  // would ever drop)
+#ifdef HSO_F32_BUILD
+  const double kRankGuard = 1e-4;
+#else
+  const double kRankGuard = 1e-10;
+#endif
   if (rule == HSO_FORCES_SPARSEQR) {
     // the literal matrix: the torso force / torque columns present and zero (ftsolver.cpp:349)
     const int cf = 6 * n + 3 * nf;

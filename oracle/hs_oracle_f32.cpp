@@ -24,6 +24,8 @@
 // HSO_FLOPCOUNT leaves the near-rank diagnostics out (they are not arithmetic of the path) and
 // with them the simulation include, which therefore follows by name
 #define HSO_FLOPCOUNT 1
+// solve_forces' rank guard is the kernel's float kFastPivotGuard (1e-4), not the fp64 1e-10
+#define HSO_F32_BUILD 1
 #define double f32r
 #include "hs_oracle.cpp"
 #include "hs_oracle_sim.cpp"

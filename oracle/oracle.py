@@ -347,14 +347,15 @@ def pd_torques(model: Model, gait: GaitParams, tsi: int, q, dq, k: float = 100.0
 def forces(model: Model, gait: GaitParams, tau_in, n_t: int = 20, k0: int = 0, ignore_reach: bool = True,
            rule: int = FORCES_KERNEL) -> dict:
     """Contact forces of all feet given motor torques tau_in [H][nmj] (ftsolver.cpp:331-378); rule: the
-    rank rule of a (numerically) rank-deficient least squares (FORCES_KERNEL or FORCES_SPARSEQR)."""
-    tau_in = np.ascontiguousarray(tau_in, dtype=np.float64)
+    rank rule of a (numerically) rank-deficient least squares (FORCES_KERNEL or FORCES_SPARSEQR). Runs on
+    the build that owns the model (float inputs for the single-precision one)."""
+    tau_in = _in(model, tau_in)
     H = tau_in.shape[0]
     cf = np.zeros((H, 3 * model.nf))
     flags = np.zeros(H, dtype=np.uint32)
-    g = gait.to_c()
-    rc = lib().hso_forces_rule(model.handle, ctypes.byref(g), n_t, k0, H, int(ignore_reach), rule, _ptr(tau_in),
-                               _ptr(cf), flags.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
+    g = _gait_in(model, gait)
+    rc = model.L.hso_forces_rule(model.handle, ctypes.byref(g), n_t, k0, H, int(ignore_reach), rule, _ptr(tau_in),
+                                 _ptr(cf), flags.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
     if rc != 0:
         raise RuntimeError(f"oracle forces failed rc={rc}")
     return dict(cf=cf, flags=flags)
@@ -362,11 +363,12 @@ def forces(model: Model, gait: GaitParams, tau_in, n_t: int = 20, k0: int = 0, i
 
 def forces_batch(model: Model, gaits: list, tau_in, n_t: int = 20, k0: int = 0, ignore_reach: bool = True,
                  n_threads: int = 1, L=None) -> dict:
-    """forces() for B rollouts on n_threads threads: tau_in [B][H][nmj] -> cf [B][H][3 nf], flags [B][H]."""
-    L = L or lib()
-    tau_in = np.ascontiguousarray(tau_in, dtype=np.float64)
+    """forces() for B rollouts on n_threads threads: tau_in [B][H][nmj] -> cf [B][H][3 nf], flags [B][H].
+    Runs on the build that owns the model (L: that build, where the caller names it)."""
+    L = L or model.L
+    tau_in = _in(model, tau_in)
     B, H = tau_in.shape[:2]
-    arr = (Gait * B)(*[g.to_c() for g in gaits])
+    arr = (Gait * B)(*[_gait_in(model, g) for g in gaits])
     cf = np.zeros((B, H, 3 * model.nf))
     flags = np.zeros((B, H), dtype=np.uint32)
     rc = L.hso_forces_batch(model.handle, arr, B, n_t, k0, H, int(ignore_reach), n_threads, _ptr(tau_in), _ptr(cf),

@@ -21,6 +21,7 @@ pytestmark = pytest.mark.gpu
 
 TAU_TOL = 1e-9
 CF_TOL = 1e-8
+FP32_TOL = 1e-3  # stated single-precision bound: |tau_f32 - tau_f64| <= 1e-3 max(1, |tau|) per step
 
 
 @pytest.fixture(scope="module")
@@ -332,8 +333,9 @@ def test_mixed_batch_matches_oracle(gpu, hmodels, oracle_mod, omodels):
 def test_forces_given_torques_match_oracle(gpu, hmodels, oracle_mod, omodels, name):
     """hs_run_forces (solve_forces, ftsolver.cpp:331-378): the kernel's reduced weighted least
     squares equals the oracle's dense Householder LS, for torques inconsistent with the motion, on
-    every step neither side flags HS_FLAG_NEAR_RANK (rank-deficient steps included: both return
-    the basic solution, HS_FLAG_GENERAL)."""
+    every step neither side flags HS_FLAG_NEAR_RANK. No step of these inputs is rank deficient: the
+    steps that drop a force component (the basic solution, HS_FLAG_GENERAL | HS_FLAG_DEPENDENT) are
+    test_forces_lifted_torso_matches_oracle's, and the fp32 build's tests/test_gpu_forces_f32_oracle.py's."""
     import torch
 
     from hslabs_amd import synth
@@ -433,8 +435,8 @@ def test_forces_bench_shape_matches_oracle(gpu, hmodels, oracle_mod, omodels):
     """solve_forces at the bench's shape (bench.py --forces: hexapod B = 4096, K = 20 fused calls of
     horizon 1, hs_run_forces_calls), with the control loop's torques perturbed so the forces are not
     just its own contact forces, against the oracle's least squares on EVERY step neither side flags
-    HS_FLAG_NEAR_RANK: forces within 1e-9 * max(1, |f|), flags identical (rank-deficient steps, basic
-    solutions flagged HS_FLAG_GENERAL, included)."""
+    HS_FLAG_NEAR_RANK: forces within 1e-9 * max(1, |f|), flags identical. The recorded runs of this shape
+    hold no rank-deficient step (the count is printed); those are test_forces_lifted_torso_matches_oracle's."""
     import torch
 
     from hslabs_amd import synth
@@ -466,6 +468,88 @@ def test_forces_bench_shape_matches_oracle(gpu, hmodels, oracle_mod, omodels):
     assert (err[~skip] < 1e-9).all(), f"forces bench shape: {(err[~skip] >= 1e-9).sum()} steps over 1e-9"
 
 
+def lifted_torso_run(gpu, hmodels, oracle_mod, omodels, name):
+    """the lifted-torso batch of `name` (forces_gpu_kit.lifted_batch) in fp64 through hs_run_forces and
+    hs_run_forces_calls, bit for bit the same, and the fp64 oracle on it: (gaits, tau, lifted rows, kernel, oracle)"""
+    import torch
+
+    from forces_gpu_kit import kernel_forces, lifted_batch
+
+    O, om = oracle_mod, omodels[name]
+    params, gaits, tau, rows = lifted_batch(O, om, name)
+    fo = O.forces_batch(om, gaits, tau, 20)
+    a = kernel_forces(gpu, hmodels[name], params, tau, torch.float64)
+    n0 = gpu.api.limb_launches()
+    b = kernel_forces(gpu, hmodels[name], params, tau, torch.float64, calls=True)
+    assert gpu.api.limb_launches() > n0  # the limb-lane kernel and its forces fixup launch
+    assert np.array_equal(a["cf"], b["cf"]) and np.array_equal(a["flags"], b["flags"])
+    return gaits, tau, rows, a, fo
+
+
+@pytest.mark.parametrize("name", ["hexapod", "myant"])
+def test_forces_lifted_torso_flags_and_drops(gpu, hmodels, oracle_mod, omodels, name):
+    """solve_forces' rank-deficient and singular-block steps in fp64: the lifted-torso cases (test_oracle.
+    LIFTED_CASES) interleaved with ordinary rollouts, through hs_run_forces and hs_run_forces_calls (the
+    limb-lane kernel, which defers these steps to its forces fixup launch), bit for bit the same. Where
+    neither side flags HS_FLAG_NEAR_RANK: equal flags (GENERAL | DEPENDENT included) and the same components
+    exactly 0; the hexapod has at least 12 such clean-drop steps (flag 592), myant 1.2 (every B_f singular,
+    full rank: the dense route without a drop) all 20. Where a side flags NEAR_RANK the dropped sets may differ
+    and the solution is not unique: the kernel's forces are finite, DEPENDENT is set exactly where a component
+    is exactly 0, and gamma (test_forces_oracle_f32: the least squares' gradient over the kernel's own kept
+    columns) is at most 10 x the oracle's largest on those steps -- a rounding residual of another
+    factorisation, not a like-for-like quantity. The forces themselves: test_forces_lifted_torso_matches_oracle."""
+    from test_forces_oracle_f32 import CLEAN_DROP, dependent_where_zero, dropped_set, gammas
+
+    O, om = oracle_mod, omodels[name]
+    gaits, tau, rows, a, fo = lifted_torso_run(gpu, hmodels, O, omodels, name)
+    assert np.isfinite(a["cf"]).all() and not (a["flags"] & 8).any()
+    skip = near(a["flags"], fo["flags"])
+    k = ~skip
+    assert np.array_equal(a["flags"][k], fo["flags"][k])
+    assert np.array_equal(dropped_set(a["cf"])[k], dropped_set(fo["cf"])[k])
+    assert dependent_where_zero(a["cf"], a["flags"])
+    n_drop = int(((fo["flags"] == CLEAN_DROP) & k).sum())
+    print(f"{name} lifted fp64: {int(k.sum())} of {k.size} steps compared, {n_drop} clean drops (flag 592), "
+          f"{int(skip.sum())} flagged HS_FLAG_NEAR_RANK")
+    if name == "hexapod":
+        assert n_drop >= 12
+    else:
+        assert k[rows].all() and (fo["flags"][rows] == 16).all()
+    if skip.any():
+        steps = [np.nonzero(skip[r])[0] for r in range(len(gaits))]
+        g_k = np.concatenate([gammas(O, om, gaits[r], tau[r], a["cf"][r], steps[r]) for r in range(len(gaits))])
+        g_o = np.concatenate([gammas(O, om, gaits[r], tau[r], fo["cf"][r], steps[r]) for r in range(len(gaits))])
+        same = (dropped_set(a["cf"]) == dropped_set(fo["cf"])).all(axis=-1)
+        print(f"{name} lifted fp64, the {int(skip.sum())} near-rank steps: gamma kernel {g_k.max():.2e}, oracle "
+              f"{g_o.max():.2e} ({g_k.max() / g_o.max():.2f} x); dropped sets equal on {int((same & skip).sum())}")
+        assert g_k.max() <= 10 * g_o.max()
+
+
+@pytest.mark.parametrize("name", ["hexapod", "myant"])
+def test_forces_lifted_torso_matches_oracle(gpu, hmodels, oracle_mod, omodels, name):
+    """The forces of the lifted-torso batches in fp64, on every step neither side flags HS_FLAG_NEAR_RANK, within
+    1e-9 max(1, max |f|) of the oracle's (the project's fp64 bound), the clean-drop steps and myant 1.2 included.
+    Measured on MI355X (profiles/forces_f32_oracle.txt): the 16 clean drops within 1.9e-13, myant's lifted steps
+    within 1.9e-14, the ordinary rollouts within 2.8e-15, and 3.6e-10 on the worst of 4 steps of the hexapod lifted
+    to 1.0 that keep all 18 columns with the smallest squared pivot 5.8e-10 .. 7.5e-10 of the largest reduced
+    diagonal (over 4 x the 1e-10 guard, so not flagged; cond(N) 4.4e10 .. 6.3e10, forces of 1.5 .. 3.8 kN). Those 4
+    steps were at 1.4e-7 .. 2.7e-6 before the dense route's corrected-semi-normal-equations step: the normal
+    equations alone lose cond(N) eps, the oracle's Householder QR sqrt(cond(N)) eps."""
+    from test_forces_oracle_f32 import CLEAN_DROP, spread
+
+    gaits, tau, rows, a, fo = lifted_torso_run(gpu, hmodels, oracle_mod, omodels, name)
+    k = ~near(a["flags"], fo["flags"])
+    err = spread(a["cf"], fo["cf"])
+    lifted = np.zeros_like(k)
+    lifted[rows] = True
+    for what, sel in (("clean drops (592)", k & (fo["flags"] == CLEAN_DROP)), ("lifted, no drop", k & lifted & ((fo["flags"] & 512) == 0)),
+                      ("ordinary rollouts", k & ~lifted)):
+        if sel.any():
+            print(f"{name} lifted fp64, {what}: {int(sel.sum())} steps, max rel {err[sel].max():.2e}, "
+                  f"{int((err[sel] >= 1e-9).sum())} at or over 1e-9")
+    assert (err[k] < 1e-9).all(), f"{name} lifted: {int((err[k] >= 1e-9).sum())} steps over 1e-9, max rel {err[k].max():.3e}"
+
+
 def test_forces_calls_fp32(gpu, hmodels):
     """The single-precision build of solve_forces: the fused form is bitwise the per-call form, and
     both stay near the fp64 forces where the least squares is well posed (no HS_FLAG_GENERAL)."""
@@ -492,30 +576,76 @@ def test_forces_calls_fp32(gpu, hmodels):
     assert np.isfinite(c32[ok]).all() and np.median(err[ok]) < 1e-3
 
 
+PD_CASES = [(0, 1), (7, 1), (19, 1), (18, 3)]  # (k0, H); H = 3 at k0 = 18 wraps tsi within the call
+
+
+def pd_run(gpu, m, params, k0, H, rng, dtype):
+    """hs_run_pd on random measurements [B][H][nmj] of `dtype`: the batch, (q, dq) on the host, (cmd, q0, dq0)"""
+    import torch
+
+    b = gpu.DeviceBatch(m, params, n_t=20, k0=k0, horizon=H, outputs=("tau",), dtype=dtype)
+    q = torch.from_numpy(rng.uniform(-np.pi, np.pi, (len(params), H, m.nmj))).to(dtype).cuda()
+    dq = torch.from_numpy(rng.uniform(-3, 3, (len(params), H, m.nmj))).to(dtype).cuda()
+    out = b.run_pd(q, dq, k=100.0, targets=True)
+    torch.cuda.synchronize()
+    assert all(o.dtype == dtype for o in out)
+    plain = gpu.DeviceBatch(m, params, n_t=20, k0=k0, horizon=1, outputs=("tau",), dtype=dtype)
+    for h in range(H):  # the step's feedforward was written too: a plain run()'s torques of the cycle's step
+        plain.k0 = (k0 + h) % 20
+        plain.run(best=False)
+        torch.cuda.synchronize()
+        assert torch.equal(b.tau[:, h], plain.tau[:, 0]), (k0, h)
+    return (q.double().cpu().numpy(), dq.double().cpu().numpy()), [o.double().cpu().numpy() for o in out]
+
+
 def test_position_control_matches_oracle(gpu, hmodels, oracle_mod, omodels):
-    """hs_run_pd (player.cpp:388-432) against the oracle's control law, over the cycle
-    incl. the wrap of tsi into [2, n_t + 1] (k0 = tsi - 2)."""
+    """hs_run_pd (player.cpp:388-432) against the oracle's control law on all three models, over the cycle
+    incl. the wrap of tsi into [2, n_t + 1] (k0 = tsi - 2), between calls and within one (H = 3)."""
     import torch
 
     from hslabs_amd import synth
 
-    m = hmodels["hexapod"]
-    params = synth.gen_params(16, "hexapod", id0=777)
+    for name in ("hexapod", "spider", "myant"):
+        m = hmodels[name]
+        params = synth.gen_params(16, name, id0=777)
+        rng = np.random.default_rng(5)
+        for k0, H in PD_CASES:
+            (q, dq), (cmd, q0, dq0) = pd_run(gpu, m, params, k0, H, rng, torch.float64)
+            for i in (0, 5, 15):
+                og = record_to_oracle_gait(oracle_mod, params[i])
+                for h in range(H):
+                    ref, rq0, rdq0 = oracle_mod.pd_torques(omodels[name], og, k0 + h + 2, q[i, h], dq[i, h], k=100.0)
+                    assert np.abs(q0[i, h] - rq0).max() < 1e-12
+                    assert np.abs(dq0[i, h] - rdq0).max() < 1e-9 * max(1, np.abs(rdq0).max())
+                    assert np.abs(cmd[i, h] - ref).max() < 1e-9 * max(1, np.abs(ref).max())
+
+
+@pytest.mark.parametrize("name", ["hexapod", "spider", "myant"])
+def test_position_control_fp32(gpu, hmodels, oracle_mod, omodels, name):
+    """hs_run_pd with HS_PREC_F32 (float q_meas, dq_meas and outputs) against the fp64 oracle's control law at
+    the float-rounded measurements: tau_cmd, q_target and dq_target within FP32_TOL, each relative to
+    max(1, |ref|) of the step (FP32_TOL's own definition). Measured on MI355X, tau_cmd / q_target / dq_target:
+    hexapod 7.4e-7 / 1.3e-6 / 3.8e-6, spider 5.4e-7 / 4.4e-7 / 5.0e-6, myant 5.1e-6 / 2.9e-6 / 3.8e-5."""
+    import torch
+
+    from hslabs_amd import synth
+
+    m = hmodels[name]
+    params = synth.gen_params(16, name, id0=777)
     rng = np.random.default_rng(5)
-    for k0 in (0, 7, 19):
-        b = gpu.DeviceBatch(m, params, n_t=20, k0=k0, horizon=1, outputs=("tau",))
-        q = torch.from_numpy(rng.uniform(-np.pi, np.pi, (16, 1, m.nmj))).cuda()
-        dq = torch.from_numpy(rng.uniform(-3, 3, (16, 1, m.nmj))).cuda()
-        cmd, q0, dq0 = b.run_pd(q, dq, k=100.0, targets=True)
-        torch.cuda.synchronize()
-        for i in (0, 5, 15):
+    worst = np.zeros(3)
+    for k0, H in PD_CASES:
+        (q, dq), out = pd_run(gpu, m, params, k0, H, rng, torch.float32)
+        for i in range(16):
             og = record_to_oracle_gait(oracle_mod, params[i])
-            ref, rq0, rdq0 = oracle_mod.pd_torques(omodels["hexapod"], og, k0 + 2, q[i, 0].cpu().numpy(),
-                                                   dq[i, 0].cpu().numpy(), k=100.0)
-            assert np.abs(q0[i, 0].cpu().numpy() - rq0).max() < 1e-12
-            assert np.abs(dq0[i, 0].cpu().numpy() - rdq0).max() < 1e-9 * max(1, np.abs(rdq0).max())
-            assert np.abs(cmd[i, 0].cpu().numpy() - ref).max() < 1e-9 * max(1, np.abs(ref).max())
-        assert torch.allclose(cmd - b.tau, cmd - b.tau)  # the step's feedforward was written too
+            for h in range(H):
+                ref = oracle_mod.pd_torques(omodels[name], og, k0 + h + 2, q[i, h], dq[i, h], k=100.0)
+                worst = np.maximum(worst, [np.abs(o[i, h] - r).max() / max(1, np.abs(r).max()) for o, r in zip(out, ref)])
+    print(f"{name} position control fp32 vs the fp64 oracle: tau_cmd {worst[0]:.2e} q_target {worst[1]:.2e} "
+          f"dq_target {worst[2]:.2e}")
+    assert worst[0] < FP32_TOL
+    assert worst[1] < FP32_TOL
+    assert worst[2] < FP32_TOL
 
 
 @pytest.mark.parametrize("sid", [8, 9, 24])
@@ -540,9 +670,6 @@ def test_complete_traj_matches_oracle(gpu, hmodels, oracle_mod, omodels, sid, tm
     rows = open(path).read().splitlines()
     assert len(rows) == 20 and len(rows[0].split()) == 2 * cfg + nmj
     np.testing.assert_allclose(np.loadtxt(path), out, rtol=1e-5, atol=1e-5)  # 6 significant digits
-
-
-FP32_TOL = 1e-3  # stated single-precision bound: |tau_f32 - tau_f64| <= 1e-3 max(1, |tau|) per step
 
 
 def contact_sets(cf, nf):
