@@ -257,6 +257,19 @@ def limb_deferred() -> int:
     return int(d.value)
 
 
+def limb_tables(model, rollout: int, n_rows: int, device=None, stream=None) -> dict:
+    """what the last fp64 call of ``model`` on ``stream`` left of ``rollout``'s per-row tables in its workspace
+    (hs_debug_limb_tables; synchronous): ktab and kvel [n_rows, 6, 3], kbig and kbad [n_rows, 6], dt"""
+    out = dict(ktab=np.zeros((n_rows, 6, 3)), kvel=np.zeros((n_rows, 6, 3)), kbig=np.zeros((n_rows, 6), np.uint8),
+               kbad=np.zeros((n_rows, 6), np.uint8))
+    dt = ctypes.c_double()
+    capi.check(capi.load().hs_debug_limb_tables(model.handle, _cuda_stream(device, stream), rollout, n_rows,
+                                                *(out[k].ctypes.data for k in ("ktab", "kvel", "kbig", "kbad")),
+                                                ctypes.addressof(dt)), "hs_debug_limb_tables")
+    out["dt"] = float(dt.value)
+    return out
+
+
 def params_array(params) -> np.ndarray:
     """list[PgsConfigParams] | structured array -> contiguous GAIT_DTYPE array."""
     if isinstance(params, np.ndarray) and params.dtype == GAIT_DTYPE:

@@ -47,7 +47,7 @@ EXPORTS = [
     "hs_comm_reduce_best", "hs_select_best_comm", "hs_pergen_rec", "hs_pergen_rec_host", "hs_model_lik",
     "hs_model_lik_host", "hs_model_fk", "hs_model_fk_host", "hs_model_get_node", "hs_model_set_torso_penalty",
     "hs_model_get_torso_penalty", "hs_model_limb_lane", "hs_limb_launches", "hs_limb_tile_launches", "hs_limb_stats",
-    "hs_limb_tile_plan_launches", "hs_limb_tile_loop_launches",
+    "hs_limb_tile_plan_launches", "hs_limb_tile_loop_launches", "hs_debug_limb_tables",
 ]
 # ... and the two whose names end in the reference's capital B (B_from_T_U, estimate_B_by_regression):
 # declared in the header and exported like the rest, listed apart because EXPORTS is compared with a
@@ -354,6 +354,8 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
     L.hs_limb_tile_plan_launches.restype = ctypes.c_int64
     L.hs_limb_tile_loop_launches.argtypes = []
     L.hs_limb_tile_loop_launches.restype = ctypes.c_int64
+    L.hs_debug_limb_tables.argtypes = [vp, vp, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, vp]
+    L.hs_debug_limb_tables.restype = ctypes.c_int
     L.hs_limb_stats.argtypes = [ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
     L.hs_abi_version.argtypes = []
     L.hs_abi_version.restype = ctypes.c_int

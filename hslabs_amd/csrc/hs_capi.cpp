@@ -567,6 +567,11 @@ int run_fused(const launch_ctx& cx, const hs_run_args& a, int32_t n_calls, step_
   // (HS_FIX_BARRIER=0: each workgroup fixes its own rollouts' items, A/B)
   const bool barrier_ok = (B + 63) / 64 <= 1024 && env_switch("HS_FIX_BARRIER", true);
   mp.prep_unit = limb ? 8 : 2;  // the rollouts' records written on the XCD whose step launches read them
+  // the rows' joint rates and range bits only where a step launch of the call reads them (the tile mapping's
+  // looping kernel): the packed, fp32 and hs_rollout_kernel launches would pay the pass's stores for nothing
+  mp.ktab_rates = 0;
+  for (int32_t i = 0; !online && i < n_chunks; i++)
+    mp.ktab_rates |= limb_tile(rt, a, (int32_t)std::min<int64_t>(CHUNK, S - (int64_t)i * CHUNK)) ? 1 : 0;
   int le = launch_setup(cx, c, mp);
   mp.red_total_mass = cx.total_mass;  // read by the launches with fix_reduce
   mp.red_rollout_mass = cx.rollout_mass;
@@ -654,6 +659,24 @@ int hs_limb_stats(int64_t* launches, int64_t* deferred) {
     if (e != hipSuccess) return hip_fail(e, "hs_limb_stats");
     *deferred = (int64_t)(n[0] + n[1]);
   }
+  return HS_OK;
+}
+
+int hs_debug_limb_tables(hs_model_t m, void* stream, int32_t rollout, int32_t n_rows, double* ktab, double* kvel,
+                         uint8_t* kbig, uint8_t* kbad, double* dt) {
+  if (!m) return fail(HS_E_ARG, "null argument");
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return hip_fail(e, "hipGetDevice");
+  const void* ws = nullptr;
+  {
+    std::lock_guard<std::mutex> lk(m->mu);
+    for (const auto& s : m->ws.live)
+      if (s.dev == dev && s.stream == stream && rollout >= 0 && (size_t)rollout < s.n) ws = s.ptr;
+  }
+  if (!ws) return fail(HS_E_ARG, "no workspace of this model, device and stream holds that rollout");
+  e = (hipError_t)hs::limb_tables_read(ws, rollout, n_rows, ktab, kvel, kbig, kbad, dt, stream);
+  if (e != hipSuccess) return hip_fail(e, "hs_debug_limb_tables");
   return HS_OK;
 }
 

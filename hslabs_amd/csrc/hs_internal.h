@@ -93,6 +93,9 @@ struct launch_map {
   // record) of samples [ktab_lo, ktab_lo + ktab_n) per rollout (ktab_range); the step launches read them. ktab_nl: limb lanes per
   // rollout the pass enumerates (the launch's largest model)
   int32_t ktab_n, ktab_lo, ktab_nl, ttab_n;
+  // the pass also stores the table rows' joint rates and range bits (RolloutWS::kvel, kbig): set by the host
+  // for a call one of whose step launches takes the limb kernel's tile loop, their only reader
+  int32_t ktab_rates = 0;
   // the preparation pass's XCD units: rollouts [u * prep_unit, (u + 1) * prep_unit) are written on XCD
   // u % 8, where the step launches read them (0 or 2: hs_rollout_kernel's two rollouts per wavefront; 8:
   // the limb-lane kernel's eight)
@@ -114,6 +117,10 @@ struct launch_map {
 
 // one fused step's general-path scratch per rollout (fused_gen holds [steps in a launch][B + 1] of them)
 size_t solve_workspace_bytes();
+// hs_debug_limb_tables' reader (hs_kernels.hip: the fp64 RolloutWS): rows [0, n_rows) of rollout's ktab, kvel,
+// kbig and kbad, packed [row][limb][3] and [row][limb], and its dt, copied to the host once `stream` has drained
+int limb_tables_read(const void* workspace, int32_t rollout, int32_t n_rows, double* ktab, double* kvel, uint8_t* kbig,
+                     uint8_t* kbad, double* dt, void* stream);
 // the samples n_calls calls of `horizon` steps from k0 read: [lo, lo + n); the IK table holds all of
 // them (n_table = n) when they fit it, else none (n_table = 0); the sample-time table the first
 // n_ttab = min(n, its capacity)

@@ -67,6 +67,23 @@ namespace hs {
 
 size_t solve_workspace_bytes() { return sizeof(SolveWS); }  // >= the fp32 build's
 
+int limb_tables_read(const void* workspace, int32_t rollout, int32_t n_rows, double* ktab, double* kvel, uint8_t* kbig,
+                     uint8_t* kbad, double* dt, void* stream) {
+  static_assert(std::is_same<real, double>::value, "the fp64 unit's RolloutWS");
+  if (n_rows < 0 || n_rows > HS_KTAB) return (int)hipErrorInvalidValue;
+  const RolloutWS* W = (const RolloutWS*)workspace + rollout;
+  hipError_t e = hipStreamSynchronize((hipStream_t)stream);
+  const auto get = [&](void* dst, const void* src, size_t n) {
+    if (e == hipSuccess && dst && n) e = hipMemcpy(dst, src, n, hipMemcpyDeviceToHost);
+  };
+  get(ktab, W->ktab, sizeof(W->ktab[0]) * n_rows);
+  get(kvel, W->kvel, sizeof(W->kvel[0]) * n_rows);
+  get(kbig, W->kbig, sizeof(W->kbig[0]) * n_rows);
+  get(kbad, W->kbad, sizeof(W->kbad[0]) * n_rows);
+  get(dt, &W->st.dt, sizeof(double));
+  return (int)e;
+}
+
 void ktab_range(int32_t k0, int32_t n_t, int32_t horizon, int64_t n_calls, int32_t* lo_out, int32_t* n_out,
                 int32_t* ttab_out) {
   // call c starts at centre sample (k0 + c horizon) % n_t + 2 (the fused and the per-step paths

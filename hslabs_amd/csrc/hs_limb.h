@@ -226,8 +226,7 @@ __device__ __attribute__((always_inline)) inline A34 limb_frame(const hs_topo* T
 }
 
 // the links' pos and ust at an outer sample of the stencil (the limb FK without the centre's features)
-// (big: a joint value sincos_k_small does not take, |x| >= 2^20 or not finite: the step is deferred)
-__device__ inline bool sincos_big(real x) { return !(fabs(x) < (real)0x1p20); }
+// (big: a joint value sincos_k_small does not take, sincos_big of hs_step_kin.h: the step is deferred)
 __device__ __attribute__((always_inline)) inline void limb_outer(const hs_topo* T, const hs_link (&LK)[3], const A34& J,
                                                                  const real* ja, real (&P)[3][3], real (&U)[3][3],
                                                                  bool& big) {
@@ -267,13 +266,6 @@ __device__ __attribute__((always_inline)) inline void outer_get(const real (&out
   }
 }
 
-// a motor's joint rate at the centre (compute_vel_traj's wrapped difference of q at t + dt and t - dt), the
-// +-pi wrap as selects
-__device__ inline real wrap_rate(real q_plus, real q_minus, real dt) {
-  const real dd = q_plus - q_minus;
-  const real lo = dd - 2 * kPi, hi = dd + 2 * kPi;
-  return (dd > kPi ? lo : (dd < -kPi ? hi : dd)) / (2 * dt);
-}
 // a joint value past sincos_k_small's range at any of the stencil's three rows defers the step
 __device__ inline bool limb_rows_big(const real* qm, const real* q0, const real* qp) {
   bool big = false;
@@ -601,6 +593,30 @@ __device__ __attribute__((always_inline)) inline void limb_centre_link(
   LDBG(dbg_r, node, g[3], 3);
 }
 
+// The tile loop's reads of what the preparation pass tabulated per table row (RolloutWS::kvel, kbig, beside
+// kbad): the centre row's joint rates and the range bits of the stencil's three FK rows, seven loads whose
+// values nothing needs before the K and D phase ends. issue() starts them; finish() is their first use (the
+// bytes enter it as opaque values: their tests formed where they are loaded would wait for the loads there).
+struct LimbTileRates {
+  real v[3];
+  uint32_t big0, big2, big4, bad;
+  __device__ __attribute__((always_inline)) inline void issue(const RolloutWS& W, int row0, int L) {
+#pragma unroll
+    for (int kk = 0; kk < 3; kk++) v[kk] = W.kvel[row0 + 2][L][kk];
+    big0 = W.kbig[row0][L];
+    big2 = W.kbig[row0 + 2][L];
+    big4 = W.kbig[row0 + 4][L];
+    bad = W.kbad[row0 + 2][L];
+  }
+  __device__ __attribute__((always_inline)) inline void finish(LimbKD& kd) {
+    asm volatile("" : "+v"(big0), "+v"(big2), "+v"(big4), "+v"(bad));
+    kd.bad = bad != 0;
+    kd.big |= (big0 | big2 | big4) != 0;
+#pragma unroll
+    for (int kk = 0; kk < 3; kk++) kd.jvel[kk] = v[kk];
+  }
+};
+
 #ifdef HS_STAMPS
 #undef HS_STAMP_GATE
 #define HS_STAMP_GATE stamp_on  // limb_tile_kd's and limb_step's: the tile loop's chosen iteration
@@ -632,6 +648,7 @@ __device__ __attribute__((always_inline)) inline void limb_tile_kd(
   real P[3][3], U[3][3];  // a limb lane's links at its centre row
   BodyS om, op, oc;       // its chain body at the three rows
   kd.own = limb && mk.own(L);
+  [[maybe_unused]] LimbTileRates tr;
   // ---- pass 0: the centre rows on the limb lanes, the first requests on the idle lanes ----
   {
     int rq = 0, fL = L;
@@ -713,6 +730,8 @@ __device__ __attribute__((always_inline)) inline void limb_tile_kd(
   }
   __builtin_amdgcn_sched_barrier(0);
   STAMP(2);
+  if constexpr (LOOP)
+    if (limb) tr.issue(W, row0, L);
   wave_sync();  // every group's outer rows
   if (limb) {
     if (kd.own) {
@@ -729,20 +748,11 @@ __device__ __attribute__((always_inline)) inline void limb_tile_kd(
 #pragma unroll
     for (int kk = 0; kk < 3; kk++)
       limb_centre_link<FORCES, false>(mk, outer, ol, l, L, kk, P[kk], U[kk], kd.Jp[kk], kd.Jz[kk], kd.fp, kd.Pc[kk], o, inv, kd.g3[kk], dbg_r);
-    kd.bad = W.kbad[row0 + 2][L] != 0;
     if constexpr (LOOP) {
-      // the range test's nine joint values and the joint rates' six in one batch of loads (the limb's five
-      // rows): loaded pair by pair behind each joint's wrap they were three more round trips per tile
-      real jq[5][3];
-#pragma unroll
-      for (int r = 0; r < 5; r++)
-#pragma unroll
-        for (int kk = 0; kk < 3; kk++) jq[r][kk] = W.ktab[row0 + r][L][kk];
-      kd.big |= limb_rows_big(jq[0], jq[2], jq[4]);
-#pragma unroll
-      for (int kk = 0; kk < 3; kk++) kd.jvel[kk] = wrap_rate(jq[3][kk], jq[1][kk], dt);
+      tr.finish(kd);
       return;
     }
+    kd.bad = W.kbad[row0 + 2][L] != 0;
     kd.big |= limb_rows_big(W.ktab[row0][L], W.ktab[row0 + 2][L], W.ktab[row0 + 4][L]);
 #pragma unroll
     for (int kk = 0; kk < 3; kk++) {

@@ -258,12 +258,12 @@ __global__ __launch_bounds__(WAVE * HS_PREP_WPB, HS_PREP_WAVES) void hs_prep_ker
                                                                    hs_run_args a, RolloutWS* __restrict__ rws,
                                                                    hs::launch_map mp) {
   __shared__ real rad_s[HS_PREP_WPB][WAVE];
-  __shared__ real q6s_s[HS_PREP_WPB][HS_PREP_ROWS][6][WAVE / 4];  // turning rows: [row][q6 entry][group] (>= 4 limbs)
-  __shared__ real tgs_s[HS_PREP_WPB][HS_PREP_ROWS][3][WAVE];      // [row][target entry][lane]
+  __shared__ real q6s_s[HS_PREP_WPB][HS_PREP_ROWS + 1][6][WAVE / 4];  // turning rows: [slot][q6 entry][group] (>= 4 limbs)
+  __shared__ real tgs_s[HS_PREP_WPB][HS_PREP_ROWS + 1][3][WAVE];  // [slot][target entry, then joint value][lane]
   const int wv = (int)threadIdx.x / WAVE, tl = (int)threadIdx.x % WAVE;  // wavefront in the block, its lane
   real(&rad)[WAVE] = rad_s[wv];
-  real(&q6s)[HS_PREP_ROWS][6][WAVE / 4] = q6s_s[wv];
-  real(&tgs)[HS_PREP_ROWS][3][WAVE] = tgs_s[wv];
+  real(&q6s)[HS_PREP_ROWS + 1][6][WAVE / 4] = q6s_s[wv];
+  real(&tgs)[HS_PREP_ROWS + 1][3][WAVE] = tgs_s[wv];
   RSTAMP(29);
   STAMP(24);
   if (blockIdx.x == 0)  // the call's fixup counters, before its step launches append to them
@@ -340,7 +340,24 @@ __global__ __launch_bounds__(WAVE * HS_PREP_WPB, HS_PREP_WAVES) void hs_prep_ker
   const real ls[3] = {(real)T->ls[0], (real)T->ls[1], (real)T->ls[2]};
   const int kind = T->lik_kind;
   const bool ir = a.ignore_reach != 0;
-  auto store_row = [&](int r, const real* ja, bool bad) {
+  // The joint rates of a chunk's first and last row (RolloutWS::kvel) read the neighbouring chunks' rows
+  // next to them. Chunks c - 1 and c + 1 of a rollout are the lane groups gl - 1 and gl + 1 of this wavefront
+  // (chunk = gi % C, gi consecutive in a wavefront), which leave their rows in LDS -- unless this group is the
+  // wavefront's first or last: then the lane computes that one row itself (hrow: the halo row, its time the
+  // same sum of dt), in one more turn of the row loop, taken only by the wavefronts that hold such a group
+  // (none at C = 5 chunks and ten groups, the hexapod's 24-row calls). A lane has at most one halo row
+  // (gpw >= WAVE / HS_LMAX groups).
+  const int n = r1 - r0;
+  const bool rates = table && mp.ktab_rates != 0;  // the call has a reader of kvel and kbig
+  const int hrow = !rates ? -1 : (gl == 0 && r0 > 0 ? r0 - 1 : (gl == gpw - 1 && r1 < mp.ttab_n ? r1 : -1));
+  const int nit = n + (__any(hrow >= 0) ? 1 : 0);
+  // slot: a row's place in the wavefront's LDS arrays, the chunk's rows in order, then the halo row
+  auto store_row = [&](int slot, int r, const real* ja, bool bad) {
+    if (rates) {
+#pragma unroll
+      for (int kk = 0; kk < 3; kk++) tgs[slot][kk][tl] = ja[kk];
+    }
+    if (slot == HS_PREP_ROWS) return;  // a halo row: its own chunk's lane stores it
     real* e = ws->ktab[r][L];
 #pragma unroll
     for (int kk = 0; kk < 3; kk++) e[kk] = ja[kk];
@@ -351,9 +368,13 @@ __global__ __launch_bounds__(WAVE * HS_PREP_WPB, HS_PREP_WAVES) void hs_prep_ker
   // (a lane's kind is fixed: the other loop's values are not live in this one)
   if (!table || straight) {
 #pragma unroll 1
-    for (int r = r0; r < r1; r++) {
-      if (r > r0) t += dt;  // the loop's next addition
-      if (L == 0) ws->t_tab[r] = t;
+    for (int it = 0; it < nit; it++) {
+      const bool mine = it < n;
+      const int r = mine ? r0 + it : hrow, slot = mine ? it : HS_PREP_ROWS;
+      if (r < 0) continue;
+      if (!mine) t = sample_time_sum(dt, mp.ktab_lo + r);
+      else if (it > 0) t += dt;  // the loop's next addition
+      if (L == 0 && mine) ws->t_tab[r] = t;
       if (table) {  // straight_ik's: J = J0 advanced by t v
         real dx, dz;
         limb_step(g, t, ts, xs, t_step, dx, dz);
@@ -361,38 +382,46 @@ __global__ __launch_bounds__(WAVE * HS_PREP_WPB, HS_PREP_WAVES) void hs_prep_ker
         real ja[3];
         bool bad;
         hip_ik_k(frame_at(J0, u, t * v), target, kind, ls, plan.ysign, ir, ja, bad);
-        store_row(r, ja, bad);
+        store_row(slot, r, ja, bad);
       }
-      if (r == r0) STAMP(27);
+      if (it == 0) STAMP(27);
     }
   } else {
     // turning or transformed gaits (kin_sample's sequence), in two passes over the rows so that the gait
     // record's values and the FK + IK's are not live together: (1) the record: the torso's q6 (lane L = 0,
     // per group) and the foot targets to LDS; (2) the torso FK (free_joint: sincos of the configured
     // angles when not turned, as free_joint_sc with the setup's), the chain, the hip frame, the limb IK
+    // (whose joint values take the targets' place in LDS)
     const LimbRec rl{v, t_step, mr, ts, xs, {pos0[0], pos0[1], pos0[2]}, tsc};
     const hs_gait_params& gp = a.params[b];
 #pragma unroll 1
-    for (int r = r0; r < r1; r++) {
-      if (r > r0) t += dt;
-      if (L == 0) ws->t_tab[r] = t;
+    for (int it = 0; it < nit; it++) {
+      const bool mine = it < n;
+      const int r = mine ? r0 + it : hrow, slot = mine ? it : HS_PREP_ROWS;
+      if (r < 0) continue;
+      if (!mine) t = sample_time_sum(dt, mp.ktab_lo + r);
+      else if (it > 0) t += dt;
+      if (L == 0 && mine) ws->t_tab[r] = t;
       real o0[3], o1[3], target[3];
       bool turned;
       gait_record<false>(g, gp, rl, t, o0, o1, turned, target);
       if (L == 0) {
         const real q6[6] = {o0[0], o0[1], o0[2], o1[0], o1[1], o1[2]};
-        for (int i = 0; i < 6; i++) q6s[r - r0][i][gl] = q6[i];
+        for (int i = 0; i < 6; i++) q6s[slot][i][gl] = q6[i];
       }
-      for (int i = 0; i < 3; i++) tgs[r - r0][i][tl] = target[i];
+      for (int i = 0; i < 3; i++) tgs[slot][i][tl] = target[i];
     }
     wave_lds_sync();
 #pragma unroll 1
-    for (int r = r0; r < r1; r++) {
+    for (int it = 0; it < nit; it++) {
+      const bool mine = it < n;
+      const int r = mine ? r0 + it : hrow, slot = mine ? it : HS_PREP_ROWS;
+      if (r < 0) continue;
       real q6[6], target[3];
-      for (int i = 0; i < 6; i++) q6[i] = q6s[r - r0][i][gl];
-      for (int i = 0; i < 3; i++) target[i] = tgs[r - r0][i][tl];
+      for (int i = 0; i < 6; i++) q6[i] = q6s[slot][i][gl];
+      for (int i = 0; i < 3; i++) target[i] = tgs[slot][i][tl];
       const A34 A0 = mul(mul(node_joint_parent(T, 0), free_joint(q6)), node_pj(T, 0));
-      if (L == 0) {  // the torso record the step launches read (kin_sample_tab)
+      if (L == 0 && mine) {  // the torso record the step launches read (kin_sample_tab)
         real* tr = ws->ktor[r];
         for (int i = 0; i < 6; i++) tr[i] = q6[i];
         store34r(A0, tr + 6);
@@ -402,8 +431,35 @@ __global__ __launch_bounds__(WAVE * HS_PREP_WPB, HS_PREP_WAVES) void hs_prep_ker
       real ja[3];
       bool bad;
       hip_ik(T, L, mul(A, node_joint_parent(T, T->limb_child[L])), target, ir, ja, bad);
-      store_row(r, ja, bad);
-      if (r == r0) STAMP(27);
+      store_row(slot, r, ja, bad);
+      if (it == 0) STAMP(27);
+    }
+  }
+  if (rates) {
+    // the rows' range bits, and the joint rates of the rows with both neighbours in the call's range: row
+    // r - 1, r, r + 1's joint values from LDS (this lane's slots; the neighbouring chunks' last and first slot
+    // on lanes tl - nli and tl + nli, or this lane's halo slot)
+    wave_lds_sync();
+    real qm[3] = {0, 0, 0}, q0[3], qp[3] = {0, 0, 0};
+    const bool lane_m = hrow == r0 - 1, lane_p = hrow == r1;  // (r0 - 1 = -1: chunk 0, no row before it)
+    if (r0 > 0)
+      for (int kk = 0; kk < 3; kk++) qm[kk] = lane_m ? tgs[HS_PREP_ROWS][kk][tl] : tgs[HS_PREP_ROWS - 1][kk][tl - nli];
+    for (int kk = 0; kk < 3; kk++) q0[kk] = tgs[0][kk][tl];
+#pragma unroll 1
+    for (int it = 0; it < n; it++) {
+      const int r = r0 + it;
+      const bool next = r + 1 < mp.ttab_n;
+      if (next)
+        for (int kk = 0; kk < 3; kk++)
+          qp[kk] = it + 1 < n ? tgs[it + 1][kk][tl] : (lane_p ? tgs[HS_PREP_ROWS][kk][tl] : tgs[0][kk][tl + nli]);
+      bool big = false;
+      for (int kk = 0; kk < 3; kk++) big |= sincos_big(q0[kk]);
+      ws->kbig[r][L] = big ? 1 : 0;
+      if (r > 0 && next) {
+        real* e = ws->kvel[r][L];
+        for (int kk = 0; kk < 3; kk++) e[kk] = wrap_rate(qp[kk], qm[kk], dt);
+      }
+      for (int kk = 0; kk < 3; kk++) qm[kk] = q0[kk], q0[kk] = qp[kk];
     }
   }
   STAMP(28);

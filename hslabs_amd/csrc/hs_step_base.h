@@ -388,6 +388,11 @@ struct RolloutWS {
   real ktab[HS_KTAB][HS_LMAX][KT_W];  // limb L's joint values at sample ktab_lo + r
   real ktor[HS_KTAB][KR_W];           // turning or transformed gaits: the torso at sample ktab_lo + r
   uint8_t kbad[HS_KTAB][HS_LMAX];     // 1: ktab[r][L]'s limb IK unreachable or failed
+  // what the limb kernel's tile loop would form from ktab again in every step that reads a row, formed once
+  // per call by the pass that writes the row (hs_prep_kernel): the motors' joint rates at an interior row c of
+  // the call's range, wrap_rate(ktab[c + 1], ktab[c - 1], dt), and a row's range bit, any sincos_big(ktab[r])
+  real kvel[HS_KTAB][HS_LMAX][KT_W];
+  uint8_t kbig[HS_KTAB][HS_LMAX];
 };
 static_assert(sizeof(SetupL) % sizeof(real) == 0, "SetupL is copied as reals");
 

@@ -357,6 +357,17 @@ __device__ inline real sample_time(const SetupL& st, const real* t_tab, int isam
   return sample_time_sum(st.dt, isample);
 }
 
+// a joint value sincos_k_small (the limb kernel's FK) does not take, |x| >= 2^20 or not finite: the step is
+// deferred (the preparation pass tabulates a row's test as RolloutWS::kbig)
+__device__ inline bool sincos_big(real x) { return !(fabs(x) < (real)0x1p20); }
+// a motor's joint rate at the centre (compute_vel_traj's wrapped difference of q at t + dt and t - dt), the
+// +-pi wrap as selects (the limb kernel's; the preparation pass tabulates it as RolloutWS::kvel)
+__device__ inline real wrap_rate(real q_plus, real q_minus, real dt) {
+  const real dd = q_plus - q_minus;
+  const real lo = dd - 2 * kPi, hi = dd + 2 * kPi;
+  return (dd > kPi ? lo : (dd < -kPi ? hi : dd)) / (2 * dt);
+}
+
 // limb FK with the new joint values (compute_dynrecs' recompute_modelnodes, model.cpp:183-201) from the
 // hip joint frame J, and the dynamic features of the links (dynrec.cpp:134-155), on the limb's
 // precombined plan (hs_topo::link): per link k the hinge frame H = J_k Rz(q_k) (mul_hinge), its body frame

@@ -853,6 +853,18 @@ int64_t hs_limb_tile_loop_launches(void);
  * two contacts, guards near their thresholds, ...) in this process; *deferred is read from the device
  * (synchronous on the current device). Either pointer may be NULL. */
 int hs_limb_stats(int64_t* launches, int64_t* deferred);
+/* Diagnostics of the preparation pass's per-row tables: what the last fp64 call of `model` on `stream` (and
+ * the current device) left for `rollout` in its workspace, rows [0, n_rows), n_rows <= 64, of the call's IK
+ * table: ktab[row][limb][3] the limbs' joint values, kvel[row][limb][3] the joint rates the limb kernel's
+ * tile loop reads (rows 1 .. n - 2 of a call of n rows; the others are never written), kbig[row][limb] a row's
+ * range bit (a joint value of 2^20 or more, or not finite), kbad[row][limb] its IK's failed-or-unreachable
+ * bit, limb stride 6, and the rollout's dt. Synchronous (the stream is drained first); a pointer may be NULL.
+ * Which rows a call writes: samples [lo, lo + n) of the period, n <= 64 (calls that read more samples keep no
+ * table). kvel and kbig are written only by a call one of whose step launches takes the tile mapping. Not to be
+ * called while another thread runs a call on the same model (the workspace may be regrown under the read). An
+ * additive export as well. */
+int hs_debug_limb_tables(hs_model_t model, void* stream, int32_t rollout, int32_t n_rows, double* ktab, double* kvel,
+                         uint8_t* kbig, uint8_t* kbad, double* dt);
 
 const char* hs_last_error(void);
 int hs_abi_version(void);

@@ -28,8 +28,8 @@ def main():
     stubs = [sys.argv[i + 1] for i, v in enumerate(sys.argv[:-1]) if v == "--stub-export"]
     if stubs:
         with open(os.path.join(dst, "hslabs_amd", "csrc", "hs_capi.cpp"), "a") as f:
-            for name in stubs:
-                f.write(f'\nextern "C" int64_t {name}(void) {{ return 0; }}\n')
+            for stub in stubs:  # (not `name`: the library's)
+                f.write(f'\nextern "C" int64_t {stub}(void) {{ return 0; }}\n')
     from hslabs_amd import build as B
     B.SRC = os.path.join(dst, "hslabs_amd", "csrc")
     out = B._compile(os.path.join(B.VARIANT_DIR, f"libhslabs_{name}.so"))
